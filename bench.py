@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — offline-render throughput of the MI355X hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload welsh-1m]
+    python bench.py --gpus N --steps K --warmup W [--workload welsh-1m] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one 256-frame block of the whole project: every voice
 ticks 256 frames (render kernels), its effect chain runs, and the mix bus sums the voice blocks
@@ -17,9 +17,18 @@ Workloads (groove_amd/projects.py):
     chain-4096    config #3   (4,096 voices + BiQuad→Chorus→Delay→Reverb per voice)
     sampler-16384 config #4   (16,384 one-shot sampler voices over a shared bank, staggered starts)
     mixed-131072  config #5   (50 % Welsh / 25 % FM / 25 % sampler)
-With the default workload on one GPU the line also carries `configs`: the other four workloads,
-each timed over its WHOLE project timeline (172 blocks; 344 for the sampler), with the bus RMS error
-of a voice sample against the CPU oracle (computed outside the timed region).
+A plain run does what its headline figure needs and nothing more: it sets up, warms up, times the K steps
+(--repeats regions), writes the last step's bus if --dump-outputs is given, and prints the line.  Everything
+else the benchmark measures runs with --full only: the issue-bound micro-benchmark of the roofline
+(tools/micro/mix_bound), the sampled comparison with the CPU oracle (`parity_vs_oracle`), the CPU baseline,
+with the default workload on one GPU `configs` (the other four workloads, each timed over its WHOLE project
+timeline — 172 blocks; 344 for the sampler — with the bus RMS error of a voice sample against the CPU oracle,
+computed outside the timed region) and `shard_curve`, and on N GPUs the line's `sections`.
+
+--dump-outputs DIR: after the timed steps, DIR/bus_last_step.npy holds what the timed path computed in its last
+step (block W+K-1 of the timeline, last timed region): the stereo mix bus a caller receives, float32 [256, 2]
+(on N GPUs rank 0's bus after the reduce).  The inputs are synthetic and fixed by the arguments, so two builds
+can be compared output for output.
 
 On one GPU (and not under a launcher) the measurement runs in a CHILD process under a watchdog: a child that has not
 printed its line in time is killed and the measurement starts again (DESIGN.md section 7 says why); the line carries
@@ -92,7 +101,7 @@ def launch_ranks(n, argv, deadline_s=None, attempts=3):
     deadline_s = deadline_s or float(os.environ.get("GROOVE_BENCH_RANKS_DEADLINE_S", "420"))
     killed = 0
     base_env = dict(os.environ)
-    if "--dry-launch" not in argv and not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
+    if "--full" in argv and "--dry-launch" not in argv and not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
         mix_bound_env(base_env)   # GPU 0's measured issue bound, before any rank starts
     for attempt in range(1, attempts + 1):
         port = str(_free_port())  # a fresh rendezvous per attempt
@@ -172,7 +181,7 @@ def supervise_rank(argv, rank, world, deadline_s=None, attempts=3):
     killed = 0
     rc_final = 3
     mb = [None]
-    if rank == 0 and "--dry-launch" not in argv and not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
+    if rank == 0 and "--full" in argv and "--dry-launch" not in argv and not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
         mb = [mix_bound_env({}, int(os.environ.get("LOCAL_RANK", "0"))).get(MIX_BOUND_ENV)]  # rank 0's GPU, before any child starts
     dist.broadcast_object_list(mb, src=0)
     if mb[0]:
@@ -802,11 +811,14 @@ class Dist:
         return float(t.item())
 
 
-def time_project(ctx, proj, bus, K, W, repeats, span_mode, dist=None):
+def time_project(ctx, proj, bus, K, W, repeats, span_mode, dist=None, budget_s=None):
     """`repeats` x (reset, W warm-up steps, K timed steps bracketed by a synchronisation — and a barrier
-    across ranks — on both sides).  Returns per-repeat wall seconds (max over ranks) and HIP-event ms per step."""
+    across ranks — on both sides).  Returns per-repeat wall seconds (max over ranks) and HIP-event ms per step.
+    `budget_s`: no further repeat starts once the timed regions have taken that long in all (long windows)."""
     walls, kerns, own = [], [], []
     for _ in range(repeats):
+        if budget_s is not None and walls and sum(walls) >= budget_s:   # (walls are the max over ranks: every rank stops alike)
+            break
         proj.reset()
         for s in range(W):
             proj.step(bus, s * FRAMES)
@@ -952,6 +964,7 @@ def roofline_block(workload, n_local, kern_ms, span_mode, fused, window=None, so
 
 
 SHORT_WINDOW_REPEATS = 7  # timed regions of a short window (see main)
+REPEATS_BUDGET_S = 5.0    # default repeats: no further timed region of the headline once they have taken this long in all
 FORM_REPEATS = 5          # ... of the materialised million-voice forms (secondary entries)
 PHASE = {"now": "start"}  # what the measurement was doing, for the message of a stall
 
@@ -960,7 +973,8 @@ def phase(text):
     PHASE["now"] = text
 
 
-def bench_workload(ctx, workload, sel, K, W, repeats, fused=True, grouped=True, render_ahead=True, dist=None, head_ahead=True, paced=None):
+def bench_workload(ctx, workload, sel, K, W, repeats, fused=True, grouped=True, render_ahead=True, dist=None, head_ahead=True, paced=None,
+                   budget_s=None):
     phase(f"timing {workload}, {len(sel)} voices, fused={fused}, grouped={grouped}, blocks {W}..{W + K - 1} x {repeats}")
     """Build the shard `sel` of a workload, time it, return the measurements (no parity, no JSON)."""
     wl = WORKLOADS[workload]
@@ -972,13 +986,19 @@ def bench_workload(ctx, workload, sel, K, W, repeats, fused=True, grouped=True, 
             else "banks in turn on the ctx stream (groove_bank_render_mix_deferred)" if proj.take_turns else "block by block")
     bus = ctx.bus((K + W) * FRAMES)
     span_mode = (fused and wl["kind"] != "chain") or (render_ahead and (wl["kind"] == "chain" or not fused))
-    walls, kerns, extra = time_project(ctx, proj, bus, K, W, repeats, span_mode, dist)
+    walls, kerns, extra = time_project(ctx, proj, bus, K, W, repeats, span_mode, dist, budget_s)
     out_bus = bus.download()[W * FRAMES:] if (dist is None or dist.rank == 0) else None
     proj.destroy()
     bus.destroy()
     order = np.argsort(walls)
     med = int(order[len(order) // 2])
     return {"walls": walls, "kerns": kerns, "median": med, "span_mode": span_mode, "bus": out_bus, "kernel_form": forms, "walk": walk, **extra}
+
+
+def dump_outputs(out_dir, out_bus):
+    """--dump-outputs: the stereo bus of the last timed step (the timed bus holds blocks W..W+K-1 of the last region)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "bus_last_step.npy"), np.ascontiguousarray(out_bus[-FRAMES:], dtype=np.float32))
 
 
 def section_plan(world, rank, workload="welsh-1m", voices=0):
@@ -1096,7 +1116,7 @@ def run_under_watchdog(argv, args, attempts=3):
     `watchdog` added; returns the exit code."""
     limit = args.watchdog_seconds or (240.0 if args.steps <= 50 else 420.0)  # a healthy run takes 40-70 s / 100-140 s
     env = dict(os.environ, GROOVE_BENCH_CHILD="1")
-    if not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
+    if args.full and not os.environ.get("GROOVE_BENCH_FAKE_STALL_ONCE"):
         mix_bound_env(env)   # this box's issue bound, measured by a fresh child BEFORE the measurement child (this process never touches the GPU)
     killed = 0
     for attempt in range(1, attempts + 1):
@@ -1135,7 +1155,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=172, help="default: one full 172-block project (44,032 frames)")
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions, each from a reset state (value = the median); default: 7 for windows of up to 40 steps, 3 otherwise")
+    ap.add_argument("--repeats", type=int, default=0, help="timed regions, each from a reset state (value = the median); default: 7 for windows of up to 40 steps, 3 otherwise, "
+                                                            f"and no further region once they have taken {REPEATS_BUDGET_S:.0f} s in all")
     ap.add_argument("--workload", default="welsh-1m", choices=sorted(WORKLOADS))
     ap.add_argument("--voices", type=int, default=0, help="override the workload's total voice count")
     ap.add_argument("--materialise", action="store_true",
@@ -1160,6 +1181,11 @@ def main():
     ap.add_argument("--no-sections", action="store_true", help="N > 1: only the measurement the flags ask for (default: strong, weak and mixed-131072 from one run)")
     ap.add_argument("--no-watchdog", action="store_true", help="run the measurement in this process (default on one GPU: in a child process that is killed and restarted if it crawls)")
     ap.add_argument("--watchdog-seconds", type=float, default=0.0, help="time allowed per attempt (default: 240 s for up to 50 steps, 420 s otherwise)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/bus_last_step.npy: the stereo bus of the last timed step (float32 [256, 2])")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the measured issue bound of the roofline, the oracle parity sample, the CPU "
+                         "baseline, `configs` and `shard_curve` (default workload, one GPU), the N-GPU `sections` (default: the headline only)")
     args = ap.parse_args()
 
     is_child = os.environ.get("GROOVE_BENCH_CHILD") == "1"
@@ -1248,12 +1274,14 @@ def measure(args, world, rank, local_rank):
     m = bench_workload(ctx, args.workload, sel, K, W, R, fused=fused, grouped=not args.interleaved,
                        render_ahead=not args.no_render_ahead, dist=dist,
                        head_ahead=False if args.no_head_ahead else ("unfused" if args.head_unfused else True),
-                       paced=False if args.no_pacing else None)
+                       paced=False if args.no_pacing else None, budget_s=None if args.repeats else REPEATS_BUDGET_S)
     line = None
     if rank == 0:
         i = m["median"]
         elapsed, kern_ms = m["walls"][i], m["kerns"][i]
         out_bus = m["bus"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out_bus)
         frames_total = K * FRAMES
         project_fps = frames_total / elapsed   # frames of the (merged) project per second: the metric, under either scaling
         n_local = hi - lo
@@ -1272,7 +1300,7 @@ def measure(args, world, rank, local_rank):
                                        + (f"weak: {V} voices per GPU, the project grows with N; value = the merged project's frames/s, voice_frames_per_s scales"
                                           if weak else "strong: the fixed project split N ways")
                                        + "), no data-path collective, 1 RCCL bus reduce per render")},
-            "timed_region": {"repeats": R, "statistic": "median repeat (by wall time)",
+            "timed_region": {"repeats": len(m["walls"]), "statistic": "median repeat (by wall time)",
                              "ms_per_step_repeats": [w / K * 1e3 for w in m["walls"]],
                              "ms_per_step_min": min(m["walls"]) / K * 1e3,
                              "kernel_ms_repeats": m["kerns"],
@@ -1293,7 +1321,7 @@ def measure(args, world, rank, local_rank):
             line["tainted"] = "the Welsh kernels counted zero-frame segments (csrc/diag.h; DESIGN.md section 7): this must not happen"
         if line["streams"].get("fast_table_misses"):
             line["tainted"] = "waves in a FAST body found a look-ahead table down (csrc/diag.h fast_table_misses): this must not happen"
-    if dist is not None and not args.no_sections and not args.materialise and not args.interleaved:
+    if dist is not None and args.full and not args.no_sections and not args.materialise and not args.interleaved:
         # ONE run of the driver's command carries all three N-GPU measurements (section_plan): the line's own measurement is one of
         # them, the other scaling mode of the same workload and config #5 follow with the same ranks and the same communicator
         plans = section_plan(world, rank, args.workload, args.voices)
@@ -1322,10 +1350,10 @@ def measure(args, world, rank, local_rank):
         dist.dist.destroy_process_group()
     if rank == 0 and world == 1:
         default_line = args.workload == "welsh-1m" and not args.voices and fused and not args.interleaved
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             line["parity_vs_oracle"] = sampled_parity(ctx, args.workload, V_total, min(K + W, 48), sample=256 if default_line else 128, fused=fused,
                                                       grouped=not args.interleaved)
-        if default_line and not args.no_configs:
+        if args.full and default_line and not args.no_configs:
             line["configs"] = [config_entry(ctx, w, R) for w in ("welsh-256", "chain-4096", "sampler-16384", "mixed-131072")]
             Kf, Wf = min(K, 20), min(W, 5)
             line["configs"].append(window_entry(ctx, "welsh-1m-library", Kf, Wf, line["ms_per_step"] if (K, W) == (Kf, Wf) else None,
@@ -1336,14 +1364,14 @@ def measure(args, world, rank, local_rank):
                                               "entity-boundary form: every voice block written to HBM (2 GB per block), mixed from the render's row sums"))
             line["configs"].append(form_entry(ctx, "welsh-1m-interleaved-materialised", Kf, Wf, False, False,
                                               "the same with patch i mod 32 on voice i (no two neighbouring voices share a patch): regrouped inside the library"))
-        if default_line and not args.no_shard_curve:
+        if args.full and default_line and not args.no_shard_curve:
             if (K, W) == (min(K, 20), min(W, 5)) and R == SHORT_WINDOW_REPEATS:
                 ms_full = line["ms_per_step"]
             else:  # (the same statistic as the shards': the median of the window's regions)
                 mf = bench_workload(ctx, "welsh-1m", sel, min(K, 20), min(W, 5), SHORT_WINDOW_REPEATS)
                 ms_full = mf["walls"][mf["median"]] / min(K, 20) * 1e3
             line["shard_curve"] = shard_curve(ctx, min(K, 20), min(W, 5), ms_full)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload)
     ctx.close()
     if rank == 0:

@@ -395,9 +395,11 @@ def test_random_patches_emulated_device_arithmetic_against_the_oracle(oracle):
     assert worst > 1e-9   # (the two are different arithmetic: fp32 feed-forward against f64)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/assets/patches/welsh"), reason="reference tree not present (this container only)")
+REF_PATCHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "assets", "patches", "welsh")   # (make_reference_data.py)
+
+
 def test_reference_patch_library_through_the_device_arithmetic(oracle):
-    """The reference's OWN Welsh patches (assets/patches/welsh/*.json: data, read where it lies) derived by the host layer (host/project.cpp,
+    """The reference's OWN Welsh patches (assets/patches/welsh/*.json: data, stored under tests/golden/reference) derived by the host layer (host/project.cpp,
     settings/src/patches.rs:87-170) and played through the device's frame text (tests/emul; the fp32 filter kind on where the host criterion
     allows it) on four keys, 40 blocks with a note-off, against the f64 oracle voice by voice: <= 5e-6 RMS, half the path's bar.  The
     library reaches where the 32 synthetic benchmark patches do not — ripples up to 10.7, a 90 Hz LFO, cutoffs of 0 and 20,000 Hz; its
@@ -415,7 +417,7 @@ def test_reference_patch_library_through_the_device_arithmetic(oracle):
     lanes = np.arange(4, dtype=np.uint32)
     on, off = T.note_events_np(lanes, keys, True), T.note_events_np(lanes, keys, False)
     played, sounding, worst = 0, 0, (0.0, "")
-    for f in sorted(glob.glob("/root/reference/assets/patches/welsh/*.json")):
+    for f in sorted(glob.glob(os.path.join(REF_PATCHES, "*.json"))):
         p, err = T.WelshParams(), C.create_string_buffer(512)
         if L.gh_welsh_params_from_patch_json(open(f).read().encode(), C.byref(p), err, 512):
             assert b"oscillator-2-track" in err.value, (f, err.value)   # the reference panics on these too (patches.rs:98)
@@ -468,8 +470,8 @@ def test_library_table_through_the_device_arithmetic(oracle, form):
 
 def test_library_table_has_the_class_proportions_of_the_reference_library():
     """profiles/r06_library_proportions.json is what tools/library_proportions.py printed for the reference's 106 patch files (counts
-    only); the synthetic table's slots, put through the library's own kind rule, land in the same base kinds in the same numbers — and in
-    the development container the script is run again on the files themselves."""
+    only); the synthetic table's slots, put through the library's own kind rule, land in the same base kinds in the same numbers — and the
+    script is run again on the stored copies of the files themselves."""
     import ctypes as C
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -489,7 +491,6 @@ def test_library_table_has_the_class_proportions_of_the_reference_library():
     assert got == want["base_kind"], (got, want["base_kind"])
     ref_f32 = sum(v for k, v in want["fp32_filter_ok"].items() if k.endswith("/ fp32"))
     assert abs(f32 - ref_f32) <= 6, (f32, ref_f32)   # (the fp32 promise is a measurement on synthetic cutoffs: close, not equal)
-    if os.path.isdir("/root/reference/assets/patches/welsh"):
-        import subprocess, sys
-        out = subprocess.run([sys.executable, os.path.join(root, "tools", "library_proportions.py"), "--json"], capture_output=True, text=True, check=True).stdout
-        assert json.loads(out) == want, "profiles/r06_library_proportions.json is stale: rerun tools/library_proportions.py --json"
+    import subprocess, sys
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "library_proportions.py"), "--json", REF_PATCHES], capture_output=True, text=True, check=True).stdout
+    assert json.loads(out) == want, "profiles/r06_library_proportions.json is stale: rerun tools/library_proportions.py --json"

@@ -188,7 +188,7 @@ def test_bench_n_gpu_code_path_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "1", "--voices", "200000",
-                        "--no-configs", "--no-shard-curve", "--no-cpu-baseline", "--no-parity", "--no-watchdog"],
+                        "--full", "--no-configs", "--no-shard-curve", "--no-cpu-baseline", "--no-parity", "--no-watchdog"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     json_lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -225,7 +225,7 @@ def test_bench_default_line_is_compact_and_carries_this_runs_bound():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GROOVE_BENCH_CHILD"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "3",
-                        "--no-configs", "--no-shard-curve"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-configs", "--no-shard-curve"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     json_lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(json_lines) == 1 and p.stdout.strip().splitlines()[-1] == json_lines[0]

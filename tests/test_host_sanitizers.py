@@ -5,8 +5,8 @@ user hands them; the reference gets memory safety from Rust (`/root/reference/se
 warns-and-continues on bad content (`songs.rs:136-139, 152-156`).  The C ABI's promise is "an error string, never a crash"
 (`include/groove_hip.h`).  Checked here with the parser half built as a program of its own (`make -C groove_amd/host asan` →
 `parse_check_asan`, no device library):
-  (a) every project and every Welsh patch the reference ships, read in place (only when /root/reference exists: this container),
-      and the committed synthetic project everywhere;
+  (a) every project and every Welsh patch the reference ships (stored under tests/golden/reference), and the committed synthetic
+      project;
   (b) truncated, bit-flipped, deeply nested and hostile-valued variants of the committed project, of a patch and of a WAV file:
       every case answers "ok" or "error: ...", the process exits 0, the sanitizers stay silent;
   (c) the oracle's known-answer tests against `oracle/liboracle_asan.so` (a child pytest with the sanitizer runtime preloaded).
@@ -21,7 +21,7 @@ import sys
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.path.join(REPO, "tests", "golden", "reference")   # the reference checkout's data files (tests/golden/make_reference_data.py)
 HOST = os.path.join(REPO, "groove_amd", "host")
 EXE = os.path.join(HOST, "parse_check_asan")
 SYNTHETIC = os.path.join(REPO, "tests", "data", "synthetic-kit-sweep.json5")
@@ -58,7 +58,6 @@ def test_committed_project_parses_clean_under_the_sanitizers(exe):
     assert devices >= 2 and notes > 10
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 def test_every_reference_project_and_patch_under_the_sanitizers(exe):
     projects = sorted(glob.glob(os.path.join(REF, "projects", "**", "*.json*"), recursive=True))
     patches = sorted(glob.glob(os.path.join(REF, "assets", "patches", "welsh", "*.json")))
@@ -134,10 +133,9 @@ PATCH_KEYS = b'''{"name": "Fuzz", "oscillator_1": {"waveform": "Sawtooth", "tune
 def test_fuzzed_patches_and_wav_headers_never_crash(exe, tmp_path):
     rng = random.Random(5)
     src = PATCH_KEYS
-    if os.path.isdir(REF):   # a real patch's shape when the tree is here; the constant above otherwise
-        some = sorted(glob.glob(os.path.join(REF, "assets", "patches", "welsh", "*.json")))
-        if some:
-            src = open(some[len(some) // 2], "rb").read()
+    some = sorted(glob.glob(os.path.join(REF, "assets", "patches", "welsh", "*.json")))   # a real patch's shape
+    if some:
+        src = open(some[len(some) // 2], "rb").read()
     files = []
     for i, c in enumerate(_variants(src, rng, 60, 150, 40) + HOSTILE[:46]):
         p = tmp_path / f"patch{i:04d}.json"

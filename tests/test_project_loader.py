@@ -1,7 +1,7 @@
 """Host logic of the compiled loader (groove_amd/host/project.cpp): project JSON/JSON5 and Welsh
-patch JSON → device-independent description.  CPU tier, no GPU calls.  Reference files are read
-only when /root/reference exists (this container); a synthetic project with the same schema
-features and content of its own is committed for the GPU box (tests/data/synthetic-kit-sweep.json5)."""
+patch JSON → device-independent description.  CPU tier, no GPU calls.  The reference's own projects, patches and (shortened)
+WAV files are stored under tests/golden/reference (tests/golden/make_reference_data.py); a synthetic project with the same schema
+features and content of its own is committed as well (tests/data/synthetic-kit-sweep.json5)."""
 import ctypes as C
 import glob
 import json
@@ -14,7 +14,7 @@ from groove_amd import abi_types as T
 from groove_amd.host_binding import HOST_LIB
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.path.join(REPO, "tests", "golden", "reference")   # the reference checkout's data files (tests/golden/make_reference_data.py)
 
 
 @pytest.fixture(scope="module")
@@ -73,13 +73,11 @@ def test_synthetic_json5_project(host):
     assert d["trips"] == [{"id": "sweep", "target": "sweep-lp", "param": "cutoff", "steps": 2, "beats": 8.0, "first_kind": 2}]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_reference_config1_project_parses(host):
     d = describe(host, path=f"{REF}/projects/demos/effects/drums-filtered-24db.json", assets=f"{REF}/assets")
     check_config1_shape(d)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_reference_demo_projects_parse(host):
     """Every demo project of the current schema generation loads (older-generation files may fail
     on schema, never on syntax)."""
@@ -95,7 +93,6 @@ def test_reference_demo_projects_parse(host):
     assert ok >= 30, (ok, schema_fail[:5])
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_fm_demo_projects_of_both_generations_load_their_synth(host):
     """projects/demos/instruments/fm-synthesizer*.json: one file in the current [midi, params] form, five (the beta sweep 0 - 100) with one
     object {"midi-in", "voice": {..}} — each yields its FM synth, its gain and its one note (the beta-100 file is what found the carrier's
@@ -108,7 +105,6 @@ def test_fm_demo_projects_of_both_generations_load_their_synth(host):
         assert d["warnings"] == 0 and d["n_notes"] >= 1, f
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_the_reference_test_projects(host):
     """projects/tests/: the invalid project "that should fail to load" fails (a device class DeviceSettings does not have, settings/src/lib.rs:
     42-46); both WAV-loading projects yield their sampler and their note (the stereo one in the one-object form of the generation before)."""
@@ -190,7 +186,6 @@ def test_welsh_patch_derivation(host):
     assert _patch(host, json.dumps(patch)).lfo_routing == T.LFO_NONE
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_all_reference_welsh_patches_derive(host):
     files = sorted(glob.glob(f"{REF}/assets/patches/welsh/*.json"))
     assert len(files) == 106
@@ -315,10 +310,9 @@ def test_wav_reader_formats_and_malformed_files(host, tmp_path):
     assert read(b"RIFF\x00\x00\x00\x00WAVEjunk")[0] == -1
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_every_reference_sample_file_decodes_like_the_standard_library(host):
     """The 81 WAV files of the reference's assets (16- and 24-bit, mono and stereo, 44.1 / 48 / 96 kHz: the drum kits' and the samplers'
-    sources) through read_wav_mono against Python's `wave` module: every frame, the mean of the channels scaled by 2^(bits-1), bit for bit."""
+    sources; stored with their first 300 frames, every chunk kept) through read_wav_mono against Python's `wave` module: every frame, the mean of the channels scaled by 2^(bits-1), bit for bit."""
     import wave
     import numpy as np
     host.gh_read_wav_mono.restype = C.c_int64
@@ -387,9 +381,9 @@ def test_sample_root_note_from_the_wav_file(host, tmp_path):
     assert root(_wav_with_chunks(extra=b"smpl\xff\xff\xff\x7f\x00\x00")) == -1   # a chunk that claims 2 GiB
     assert root(_wav_with_chunks(extra=b"LIST\x03\x00\x00\x00abc\x00" + smpl_chunk(48))) == 48   # odd-sized chunk before it: padded
     assert host.gh_read_wav_root_note(str(tmp_path / "missing.wav").encode()) == -1
-    if os.path.exists(REF):   # the reference's own pair of files (test-data/samples): one carries an acid chunk with root note 57
-        assert host.gh_read_wav_root_note(f"{REF}/test-data/samples/riff-acidized.wav".encode()) == 57
-        assert host.gh_read_wav_root_note(f"{REF}/test-data/samples/riff-not-acidized.wav".encode()) == -1
+    # the reference's own pair of files (test-data/samples): one carries an acid chunk with root note 57
+    assert host.gh_read_wav_root_note(f"{REF}/test-data/samples/riff-acidized.wav".encode()) == 57
+    assert host.gh_read_wav_root_note(f"{REF}/test-data/samples/riff-not-acidized.wav".encode()) == -1
 
 
 RAW_AND_TOY = """{
@@ -423,7 +417,6 @@ def test_welsh_raw_toy_instrument_and_sampler_parse(host):
     assert kinds["s-1"]["kind"] == "sampler" and kinds["s-1"]["name"] == "pluck.wav"
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
 def test_the_reference_sampler_demo_parses_with_its_roots(host):
     """projects/demos/instruments/sampler.json: two samplers over one stereo file, roots 587.33 Hz and 86 Hz."""
     d = describe(host, path=f"{REF}/projects/demos/instruments/sampler.json", assets=f"{REF}/assets")

@@ -2,7 +2,7 @@
 # config #3 inside whole bench.py runs (fresh processes): hunting the run whose chain-4096 repeats all read ~0.06 ms
 cd "${GRAFT_REPO_ROOT:-.}"
 for i in $(seq 1 ${N:-12}); do
-python3 bench.py --no-cpu-baseline --no-shard-curve "$@" > /dev/null 2>&1
+python3 bench.py --full --no-cpu-baseline --no-shard-curve "$@" > /dev/null 2>&1
 python3 - <<'P'
 import json
 d=json.load(open("bench_detail.json"))

@@ -1,5 +1,5 @@
-"""Class proportions of the reference's Welsh patch library (assets/patches/welsh/*.json under /root/reference: DATA, read where it
-lies, in the development container only — nothing of a file is copied; the output is counts).
+"""Class proportions of the reference's Welsh patch library (its assets/patches/welsh/*.json: DATA, stored under
+tests/golden/reference by tests/golden/make_reference_data.py; another directory of patch files can be named; the output is counts).
 
 Every file goes through the host layer's derivation (host/project.cpp welsh_params_from_patch_json = settings/src/patches.rs:87-170)
 and the library's own kind rule (csrc/dsp_core.h welsh_base_kind / welsh_body_classes via tests/emul): which of the six base kinds
@@ -7,7 +7,7 @@ and the library's own kind rule (csrc/dsp_core.h welsh_base_kind / welsh_body_cl
 `groove_amd/patches.py` LIBRARY_* holds the table this prints (the workload `welsh-1m-library`: synthetic patches whose CLASS
 proportions follow these counts).
 
-    python3 tools/library_proportions.py [--json]
+    python3 tools/library_proportions.py [--json] [PATCH_DIR]
 """
 import collections
 import ctypes as C
@@ -39,7 +39,8 @@ def classify(p, sr=44100):
 def main():
     host = C.CDLL(os.path.join(REPO, "groove_amd", "host", "libgroove_host.so"))
     host.gh_welsh_params_from_patch_json.argtypes = [C.c_char_p, C.POINTER(T.WelshParams), C.c_char_p, C.c_size_t]
-    files = sorted(glob.glob("/root/reference/assets/patches/welsh/*.json"))
+    pdir = next((a for a in sys.argv[1:] if not a.startswith("--")), os.path.join(REPO, "tests", "golden", "reference", "assets", "patches", "welsh"))
+    files = sorted(glob.glob(os.path.join(pdir, "*.json")))
     base, edge, f32, oscs, lfo_cls, skipped = collections.Counter(), collections.Counter(), collections.Counter(), collections.Counter(), collections.Counter(), 0
     sync = retune_env = 0
     for f in files:
