@@ -877,31 +877,24 @@ GROOVE_HD float osc_value_classed(uint32_t w, uint64_t phase, uint64_t duty64, f
 // `tab` (a wave-uniform 0 / 1 in an SGPR; HOIST frames of the uniform kernels only): this segment's filter coefficients come from the
 // wave's look-ahead table (kernels.h "coefficient look-ahead"), so the frame neither evaluates the filter envelope nor derives a cutoff
 // percent from it.  (An integer, not a bool: as a bool the flag lived in a lane mask and its negation went through two vector instructions.)
-// AMPTAB (with `tab`): the table's entries carry the AMPLITUDE envelope's value of the frame too (`tab_amp`; the caller sets `tab` only
-// where the live lanes agree on BOTH envelopes' stages): the same env_shape on the same counter, from the lane that filled the entry.
 template <bool FIRST, bool RETUNE, int LFO_MODE = LFO_F64, int C1 = OSC_ANY, int C2 = OSC_ANY, int CL = OSC_ANY, bool SEGMENT = false, bool REST = false,
-          bool HOIST = false, bool AMPTAB = false, int TABS = 0, bool NO_PCT = false>
+          bool HOIST = false, int TABS = 0, bool NO_PCT = false>
 GROOVE_HD bool welsh_frame_front(const WelshParams& p, WelshState& s, WelshScratch& sc, float& sum, float& a, float& pct, bool& retune, float& lfo, uint32_t tab = 0u,
-                                 uint32_t ltab = 0u, double tab_mod = 0.0, float tab_lfo = 0.0f, float tab_amp = 0.0f) {
+                                 uint32_t ltab = 0u, double tab_mod = 0.0, float tab_lfo = 0.0f) {
   static_assert(!HOIST || (SEGMENT && !FIRST), "hoisted counters belong to a segment");
   if (SEGMENT && HOIST) {
     // env_shape with the segment's constants (welsh_segment_start_hoisted): two operations per envelope and frame
-    // (The amplitude envelope's value from the table was first tried with a flag and a branch of its own, before the frame loop ran in
-    // chunks: 0.362 - 0.373 against 0.354 - 0.357 ms per block in one job.  Lost in that form; AMPTAB rides on `tab`.)
-    if (!AMPTAB) { s.amp.value = env_shape(sc.ta, s.amp.A, sc.ac1, sc.ac2); sc.ta += 1.0f; }
+    // (the amplitude envelope's value from the look-ahead table was measured and lost: docs/HISTORY.md)
+    s.amp.value = env_shape(sc.ta, s.amp.A, sc.ac1, sc.ac2); sc.ta += 1.0f;
     // NO_PCT (welsh_frame's retuned HOIST frames): the filter envelope, the cutoff percent and the coefficients are one block behind ONE
     // test of `tab` there, not three tests here and there (each test three scalar instructions and, on a table frame, a taken branch)
     if (NO_PCT) {
     } else if (welsh_tab_is_off<TABS, 1>(tab)) {
-      if (AMPTAB) { s.amp.value = env_shape(sc.ta, s.amp.A, sc.ac1, sc.ac2); sc.ta += 1.0f; }
       s.fil.value = env_shape(sc.tf, s.fil.A, sc.fc1, sc.fc2); sc.tf += 1.0f;
 #if defined(__HIP_DEVICE_COMPILE__)
       // keeps `tab` a scalar BRANCH: if-converted, a table frame still evaluated the envelope and the percent and selected them away
       asm volatile("" : "+v"(s.fil.value));
-      if (AMPTAB) asm volatile("" : "+v"(s.amp.value));
 #endif
-    } else if (AMPTAB) {
-      s.amp.value = tab_amp;
     }
   } else if (SEGMENT) {
     env_advance(s.amp);
@@ -1196,15 +1189,15 @@ GROOVE_HD void welsh_frame_back(const WelshParams& p, Lp24StateD& filt, const Lp
 // after the segment (welsh_segment_end) — and an unused LFO's phase moves there too: two conversions, two integer
 // adds and a 64-bit add less on every frame.
 template <bool FIRST, bool RETUNE, int LFO_MODE = LFO_F64, int C1 = OSC_ANY, int C2 = OSC_ANY, int CL = OSC_ANY, bool SEGMENT = false, bool REST = false,
-          bool HOIST = false, bool F32FILT = false, bool AMPTAB = false, int TABS = 0>
+          bool HOIST = false, bool F32FILT = false, int TABS = 0>
 GROOVE_HD void welsh_frame(const WelshParams& p, WelshState& s, const RenderConsts& rc,
-                           WelshScratch& sc, float& L, float& R, uint32_t tab = 0u, uint32_t ltab = 0u, double tab_mod = 0.0, float tab_lfo = 0.0f, float tab_amp = 0.0f) {
+                           WelshScratch& sc, float& L, float& R, uint32_t tab = 0u, uint32_t ltab = 0u, double tab_mod = 0.0, float tab_lfo = 0.0f) {
   static_assert(!(F32FILT && LFO_MODE == LFO_F64), "the exact-f64 kinds (resonance routing) keep the f64 filter");
   float sum, a, pct, lfo;
   bool retune;
   // (tab: the caller has put this frame's coefficients into sc.coef / sc.coef_f already — kernels.h "coefficient look-ahead")
-  constexpr bool LATE = HOIST && RETUNE && LFO_MODE != LFO_F64 && !AMPTAB; // filter envelope -> percent -> coefficients in one block, below
-  if (!welsh_frame_front<FIRST, RETUNE, LFO_MODE, C1, C2, CL, SEGMENT, REST, HOIST, AMPTAB, TABS, LATE>(p, s, sc, sum, a, pct, retune, lfo, tab, ltab, tab_mod, tab_lfo, tab_amp)) { L = 0.0f; R = 0.0f; return; }
+  constexpr bool LATE = HOIST && RETUNE && LFO_MODE != LFO_F64; // filter envelope -> percent -> coefficients in one block, below
+  if (!welsh_frame_front<FIRST, RETUNE, LFO_MODE, C1, C2, CL, SEGMENT, REST, HOIST, TABS, LATE>(p, s, sc, sum, a, pct, retune, lfo, tab, ltab, tab_mod, tab_lfo)) { L = 0.0f; R = 0.0f; return; }
   if constexpr (LATE) {
     if (welsh_tab_is_off<TABS, 1>(tab)) {
       // welsh_frame_front's statements, in its order: the filter envelope's value of the frame, then the percent from it — or from the LFO

@@ -201,13 +201,9 @@ struct groove_ctx {
   uint32_t tp_max_voices = kTpMaxVoices; // Welsh banks up to this size render time-parallel (welsh_tp.h); GROOVE_TP_MAX_VOICES overrides, 0 = never
   uint32_t fx_tp_max_lanes = 4096;       // IIR effect banks of up to this many lane-channels (half as many for the 24 dB low-pass) run time-parallel (fx_tp.h: measured crossovers, tools/fx_bench.py)
   // Mid-size Welsh banks (too big for the time-parallel form, too small to fill the chip with one voice-wave per wavefront):
-  // the ROLE-SPLIT kernel (welsh_split.h: three wavefronts per 64 voices, pipelined over the block's frames) for banks of up
+  // the ROLE-SPLIT kernel (welsh_split.h: four wavefronts per 64 voices, pipelined over the block's frames) for banks of up
   // to this many virtual waves; 0 = never.  groove_set_split_max_waves.
-  uint32_t split_max_waves = 1024;      // 65,536 voices = one workgroup (twelve wavefronts) per CU; measured (round 3, blocks 5-24): 20,000 voices 0.120 -> 0.090 ms per block, 32,768 0.119 -> 0.090, 65,536 0.123 -> 0.095; 80,000 (a second round of workgroups) 0.135 -> 0.153: not above
-  uint32_t split2_max_waves = 1024;      // (= split_max_waves: off by default since the end of round 6 — with the FAST copies of its bodies the all-kinds kernel walks a block of 80,000 - 125,000 voices in 0.091 - 0.095 ms where this form takes 0.119 - 0.125, in one job, tools/ab_env.sh; GROOVE_SPLIT2_MAX_WAVES=2048 brings it back.)  Banks above split_max_waves and up to this many virtual waves (131,072 voices until then): the TWO-role form, front + tangent | back — two workgroups of eight wavefronts per CU, so one round still; measured (blocks 5-24): 100,000 voices 0.1385 -> 0.134 ms per block, 125,000 0.145 -> 0.137 (three roles there: 0.164 / 0.165; two roles at 65,536: 0.106 against three roles' 0.095)
-  int split_roles = 4;                   // roles of the form used up to split_max_waves: four (ctl | osc | tangent + quotients | back), measured against three
-                                         // (front | tangent | back) in one job: 32,768 voices 0.0830 against 0.0888 ms per block, 65,536 0.0846-0.0855 against
-                                         // 0.0903, config #5 0.1003-0.1008 against 0.0999-0.1001.  GROOVE_SPLIT_ROLES=3 / 2: A/B
+  uint32_t split_max_waves = 1024;      // 65,536 voices = one workgroup (sixteen wavefronts) per CU; measured (round 3, blocks 5-24): 20,000 voices 0.120 -> 0.090 ms per block, 32,768 0.119 -> 0.090, 65,536 0.123 -> 0.095; 80,000 (a second round of workgroups) 0.135 -> 0.153: not above
   uint32_t pipeline_min_waves = 3800;   // banks at least this long (~243,000 voices; 7,000 = ~450,000 until the end of round 6: with the FAST copies of the bodies in both kernels the crossover moved down — in one job, tools/ab_env.sh, mix kernel against all-kinds kernel: 200,000 voices 0.114 against 0.110 ms per block, 250,000 0.120 against 0.121 - 0.123, 300,000 0.125 against 0.158, 400,000 0.139 against 0.188, 500,000 0.164 against 0.212) run the mix kernel (one launch per base kind before round 6) and pipeline their fused blocks; smaller ones take the all-kinds kernel (round 2, blocks 5-44 of the timeline: 300,000 voices 0.275 -> 0.250 ms per block, 500,000 0.357 -> 0.342; 600,000 0.372 against 0.400.  Round 5: the per-kind kernels alone carry the fp32 filter kind and the crossover moved down from ~550,000 — the driver's window, in-job, per-kind against all-kinds: 500,000 voices 0.271 against 0.281, 420,000 0.246 against 0.244, 350,000 0.223 against 0.225: profiles/r05_pipeline_threshold_ab.log)
   // How many of the bank streams exist and are handed out.  Three: with the ctx stream and the four
   // kind streams that is eight streams; a ninth lands on a hardware queue that already carries one of the others, and a
@@ -220,7 +216,6 @@ struct groove_ctx {
   // used to be the fourth kind stream and is now a placeholder nobody uses.
   int kind_streams = 3;
   uint32_t look_ahead = 3u; // RenderConsts::look: bit 0 the coefficient look-ahead, bit 1 the LFO look-ahead (kernels.h); GROOVE_LOOK_AHEAD=<bits>, groove_set_look_ahead (tests render the same bank with and without)
-  bool mix_kernel = true; // big Welsh banks: the four class-specialised kinds in three balanced launches (kernels.h, the MIX kernel); GROOVE_MIX_KERNEL=0: one launch per base kind (round 5's form, for A/B runs)
   int next_stream_slot = 0;             // round-robin side-stream assignment of single-kernel banks
   uint32_t fm_tp_max_voices = kFmTpMaxVoices;
   // Welsh banks of at least this many voices whose adjacent pairs share a patch render two voices per wavefront
@@ -1224,7 +1219,6 @@ static int init_impl(int device_ordinal, const uint8_t* comm_id, int rank, int w
   ctx->device = device_ordinal;
   if (const char* e = std::getenv("GROOVE_FX_SEQ_ALLPASS")) ctx->seq_allpass = e[0] == '1';
   if (const char* e = std::getenv("GROOVE_SAFE_STREAMS")) ctx->safe_streams = e[0] == '1';
-  if (const char* e = std::getenv("GROOVE_MIX_KERNEL")) ctx->mix_kernel = e[0] != '0';
   if (const char* e = std::getenv("GROOVE_LOOK_AHEAD")) ctx->look_ahead = (uint32_t)std::strtoul(e, nullptr, 10) & 7u;
   if (const char* e = std::getenv("GROOVE_SYNC_TIMEOUT_MS")) ctx->sync_timeout_ms = (uint32_t)std::strtoul(e, nullptr, 10);
   if (const char* e = std::getenv("GROOVE_FM_TP_VPW4_MIN_VOICES")) ctx->fm_tp_vpw4_min_voices = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -1232,8 +1226,6 @@ static int init_impl(int device_ordinal, const uint8_t* comm_id, int rank, int w
   if (const char* e = std::getenv("GROOVE_FX_CHUNKED_ALLPASS")) ctx->chunked_allpass = e[0] == '1';
   if (const char* e = std::getenv("GROOVE_TP_MAX_VOICES")) ctx->tp_max_voices = (uint32_t)std::strtoul(e, nullptr, 10);
   if (const char* e = std::getenv("GROOVE_SPLIT_MAX_WAVES")) ctx->split_max_waves = (uint32_t)std::strtoul(e, nullptr, 10);   // (A/B runs: tools/ab_env.sh)
-  if (const char* e = std::getenv("GROOVE_SPLIT2_MAX_WAVES")) ctx->split2_max_waves = (uint32_t)std::strtoul(e, nullptr, 10);
-  if (const char* e = std::getenv("GROOVE_SPLIT_ROLES")) { const int r = std::atoi(e); ctx->split_roles = r == 2 || r == 4 ? r : 3; }
   if (const char* e = std::getenv("GROOVE_F32_FILTER")) ctx->f32_filter = e[0] != '0'; // (A/B and the bit-identity tests between kernel forms)
   if (const char* e = std::getenv("GROOVE_PIPELINE_MIN_WAVES")) ctx->pipeline_min_waves = (uint32_t)std::strtoul(e, nullptr, 10); // tests force the pipeline on small banks
   bool ok = hipSetDevice(device_ordinal) == hipSuccess;
@@ -1334,7 +1326,7 @@ int groove_debug_info(groove_ctx* ctx, char* out, size_t cap) {
   DiagCounters dc{};
   GHIP(ctx, ctx_memcpy(ctx, &dc, ctx->d_diag, sizeof(dc), hipMemcpyDeviceToHost));
   std::string diag = "\"host_waits\": " + std::to_string(ctx->host_waits) + ", \"host_waits_blocked\": " + std::to_string(ctx->host_waits_blocked) + ", \"host_wait_ms\": " + std::to_string((double)ctx->host_wait_ns * 1e-6) +
-                     ", \"zero_segments\": " + std::to_string(dc.zero_segments) + ", \"fast_table_misses\": " + std::to_string(dc.fast_table_misses) + ", \"fast_waves\": " + std::to_string(dc.fast_waves) + ", \"source_hash\": \"" GROOVE_SOURCE_HASH "\", \"mix_kernel\": " + (ctx->mix_kernel ? "true" : "false");
+                     ", \"zero_segments\": " + std::to_string(dc.zero_segments) + ", \"fast_table_misses\": " + std::to_string(dc.fast_table_misses) + ", \"fast_waves\": " + std::to_string(dc.fast_waves) + ", \"source_hash\": \"" GROOVE_SOURCE_HASH "\"";
 #ifdef GROOVE_DIAG_SHADOW_IN_MIN
   diag += ", \"diag_build\": \"GROOVE_DIAG_SHADOW_IN_MIN\", \"shadow_zero_lanes\": " + std::to_string(dc.shadow_zero_lanes) + ", \"shadow_zero_waves\": " + std::to_string(dc.shadow_zero_waves) + ", \"records\": [";
   for (uint32_t i = 0; i < std::min(dc.records, kDiagRecords); ++i) {
@@ -1692,11 +1684,8 @@ static UniformArgs uniform_args(const groove_bank* b, float* out, float* rows, u
 // bank is mid-size, for the workgroups of the four class-specialised base kinds (the workgroup list is sorted by kind: they
 // come first); the rest, or everything, through the all-kinds kernel.
 static bool use_split(const groove_bank* b, uint32_t frames) {
-  const groove_ctx* ctx = b->ctx;
-  if (ctx->split_max_waves == 0) return false; // "never" switches both forms off
-  return b->kind == BANK_WELSH && b->n_vwaves && !use_tp(b, frames) && b->n_vwaves <= std::max(ctx->split_max_waves, ctx->split2_max_waves) && frames >= 2 * kSplitChunk;
+  return b->kind == BANK_WELSH && b->n_vwaves && !use_tp(b, frames) && b->n_vwaves <= b->ctx->split_max_waves && frames >= 2 * kSplitChunk;
 }
-static int split_roles_of(const groove_bank* b) { return b->n_vwaves <= b->ctx->split_max_waves ? b->ctx->split_roles : 2; }
 static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
 static void launch_small_uniform(groove_bank* b, const UniformArgs& a, hipStream_t st, bool fused, uint32_t frames, hipEvent_t done = nullptr /* bound to the last launch */) {
   // the workgroup list is sorted by kind: the four class-specialised base kinds first, then the two exact-f64 ones
@@ -1707,12 +1696,7 @@ static void launch_small_uniform(groove_bank* b, const UniformArgs& a, hipStream
     UniformArgs s = a;
     s.n_wgs = n_spec;
     const hipEvent_t d = (n_f64[0] || n_f64[1]) ? nullptr : done;
-    if (use_split(b, frames)) {
-      const int roles = split_roles_of(b);
-      if (roles == 4) launch_welsh_split4(s, b->d_wg_base, st, fused, d);
-      else if (roles == 3) launch_welsh_split(s, b->d_wg_base, st, fused, d);
-      else launch_welsh_split2(s, b->d_wg_base, st, fused, d);
-    }
+    if (use_split(b, frames)) launch_welsh_split4(s, b->d_wg_base, st, fused, d);
     else if (fused) launch_welsh_uniform_any(s, b->d_wg_base, st, d);
     else launch_welsh_uniform_any_unfused(s, b->d_wg_base, st, d);
   }
@@ -1903,16 +1887,15 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
       for (int c = 0; c < kClassCombos; ++c) count[base] += b->wgs_of_kind[base * kClassCombos + c];
       at += count[base];
     }
-    const bool mix = ctx->mix_kernel; // (the MIX kernel, block-writing form: kernels.h; the exact-f64 kinds keep their per-kind kernels)
-    for (int k = kBaseKinds - 1; k >= 0; --k) { // most expensive kind first
-      if (mix && k < 4) continue;
+    // the exact-f64 kinds keep their per-kind kernels, most expensive first; the other four take the MIX kernel (block-writing form: kernels.h)
+    for (int k = kBaseKinds - 1; k >= 4; --k) {
       if (!count[k]) continue;
       hipStream_t st = begin(k);
       UniformArgs a = uniform_args(b, dst, rows, offset[k], chs, frames, count[k]);
       launch_welsh_kind(k, a, st, false);
       end(k);
     }
-    for (int sec = 2; mix && sec >= 0; --sec) {
+    for (int sec = 2; sec >= 0; --sec) {
       if (!b->mix_cnt[sec]) continue;
       hipStream_t st = begin(sec);
       UniformArgs a = uniform_args(b, dst, rows, 0, chs, frames, b->mix_cnt[sec]);
@@ -2024,14 +2007,14 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
   uint32_t count[kSideStreams] = {}, offset[kSideStreams] = {}; // per stream: Welsh base kinds first, then the bank streams
   // The MIX kernel (kernels.h; round 6): the four class-specialised base kinds in three launches, one per kind stream, each over a
   // third of their workgroups (every third entry of the kind-sorted list); the exact-f64 kinds keep their per-kind kernels.
-  const bool mix = uniform && ctx->mix_kernel;
   if (uniform) {
     for (uint32_t base = 0, at = 0; base < (uint32_t)kBaseKinds; ++base) {
       offset[base] = at;
       for (int c = 0; c < kClassCombos; ++c) count[base] += b->wgs_of_kind[base * kClassCombos + c];
       at += count[base];
     }
-    if (mix) { for (int sec = 0; sec < 3; ++sec) count[sec] = b->mix_cnt[sec]; count[3] = 0; }
+    for (int sec = 0; sec < 3; ++sec) count[sec] = b->mix_cnt[sec]; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds
+    count[3] = 0;
   } else {
     count[b->stream_slot] = rows; // one kernel, on this bank's side stream (the loop below runs once)
   }
@@ -2064,7 +2047,7 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
     // the block's "render done" event completes with the render kernel itself (kernels.h launch_bound): no record packet between
     // this block's kernel and the next block's on the stream
     const hipEvent_t done = ctx->bind_events ? b->ev_render_done[k][slot] : nullptr;
-    if (uniform && mix && k < 3) {
+    if (uniform && k < 3) {
       UniformArgs a = uniform_args(b, b->d_pipe_part[slot], b->d_pipe_part[slot], 0, 0, frames, count[k]);
       const size_t o = b->wg_list_cap + b->mix_off[k]; // the section's entries of the striped copies (welsh_upload_params)
       a.wg_list = b->d_wg_list + o; a.wg_cls = b->d_wg_cls + o; a.wg_f32 = b->d_wg_f32 + o;
@@ -2183,7 +2166,7 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
   if (frames == 0) return 0;
   // (several banks of a small project may take turns on the ctx stream this way — each render carries the reduction of the one
   // before it, in submission order — instead of side by side on side streams with their cross-queue waits: the caller's choice)
-  // A Welsh bank too big for the time-parallel form and too small for the per-kind pipeline (the all-kinds or a role-split
+  // A Welsh bank too big for the time-parallel form and too small for the per-kind pipeline (the all-kinds or the role-split
   // kernel on the ctx stream, then two reduction launches in line behind it: ~18 us of a 125,000-voice shard's 130) takes the same
   // deferral, the next block's kernel summing the rows — when the launch that would carry them exists (some workgroup of the four
   // class-specialised kinds) and the rows are few enough (deferred_rows_of).
@@ -2323,12 +2306,9 @@ const char* groove_bank_kernel_form(groove_bank* b, uint32_t frames, int fused) 
   if (!b->n_vwaves) return "welsh_render_kernel (per-lane parameters)";
   const bool pipelined = fused && (b->n_vwaves >= ctx->pipeline_min_waves || ctx->pipeline_min_waves <= 1);
   if (b->n_vwaves >= ctx->pipeline_min_waves || (fused && ctx->pipeline_min_waves <= 1))
-    return pipelined ? (ctx->mix_kernel ? "welsh_render_uniform_mix_kernel (big-bank form: three launches per block over thirds of the kind-sorted workgroups, one launch per base kind for the exact-f64 kinds only; class-specialised bodies, blocks pipelined)"
-                                        : "welsh_render_uniform_kernel (one launch per base kind, class-specialised bodies, blocks pipelined)")
+    return pipelined ? "welsh_render_uniform_mix_kernel (big-bank form: three launches per block over thirds of the kind-sorted workgroups, one launch per base kind for the exact-f64 kinds only; class-specialised bodies, blocks pipelined)"
                      : "welsh_render_uniform_kernel (one launch per base kind, class-specialised bodies)";
-  if (use_split(b, frames) && split_roles_of(b) == 4) return "welsh_render_split4_kernel (role-split: four wavefronts per 64 voices, pipelined over the frames)";
-  if (use_split(b, frames)) return split_roles_of(b) == 3 ? "welsh_render_split_kernel (role-split: three wavefronts per 64 voices, pipelined over the frames)"
-                                                            : "welsh_render_split_kernel (role-split: two wavefronts per 64 voices, pipelined over the frames)";
+  if (use_split(b, frames)) return "welsh_render_split4_kernel (role-split: four wavefronts per 64 voices, pipelined over the frames)";
   return "welsh_render_uniform_any_kernel (all base kinds in one launch, class-specialised bodies)";
 }
 int groove_bank_reset(groove_bank* b) {

@@ -80,25 +80,8 @@ __device__ __forceinline__ void soa_store(uint32_t* __restrict__ buf, uint32_t n
 /* (A second copy of the frame loop for waves whose 64 lanes all sound — no exec-mask region round the frame, no two moves of zero in front of
    it — was measured twice in round 6 and lost twice: in the shared bodies 0.523 against 0.350 ms per block (the doubled loops spilled), inside
    the FAST copies 0.3240 - 0.3258 against 0.3138 - 0.3174.  Not in the source any more.) */
-#ifndef GROOVE_FAST_TABLE_LOOP
-#define GROOVE_FAST_TABLE_LOOP 1 /* segments whose look-aheads are all up run a frame loop of their own, compiled without the flag tests (run_frames_segmented `fast`):
-                                    1 in the F32 kinds' fp32-filter bodies; 2 also in the smooth-f64 kinds' fp32-filter bodies with a sine / triangle LFO (no scratch access in
-                                    either loop, and nothing on the clock: 0.3367 - 0.3419 against 0.3344 - 0.3383 ms per block); 3 also in the F32 kinds' f64-filter bodies (the
-                                    library-proportioned bank 0.348 -> 0.387: their other loop spills); 0: one loop everywhere.  One job each, tools/ab_bench.sh. */
-#endif
-#ifndef GROOVE_AMP_IN_TABLE
-#define GROOVE_AMP_IN_TABLE 0 /* 1: the retuned kinds' table entries carry the amplitude envelope's value of the frame too (TabLayout::kAmp, welsh_frame's AMPTAB: the
-                                 table flag then also asks for a shared amplitude stage).  Three vector instructions a table frame less — and nothing on the clock, three times:
-                                 with a flag and a branch of its own before the frame loop ran in chunks (0.362 - 0.373 against 0.354 - 0.357 ms per block), and riding
-                                 on the coefficient flag after (0.3464 - 0.3512 against 0.3483 - 0.3502; library 0.3469 - 0.3565 against 0.3494 - 0.3533), and with the FAST copies, whose promise then
-                                 covers the amplitude envelope's record too (0.3175 - 0.3339 against 0.3098 - 0.3138); one job each, tools/ab_bench.sh.  The frame is not short of issue slots at that point; left in the source, off. */
-#endif
-#ifndef GROOVE_LFO_LOOKAHEAD
-#define GROOVE_LFO_LOOKAHEAD 1 /* the smooth-f64 kinds' LFO look-ahead (below, "LFO look-ahead"); 0: every lane advances its LFO's recurrences (A/B builds) */
-#endif
-#ifndef GROOVE_COEF_LOOKAHEAD
-#define GROOVE_COEF_LOOKAHEAD 1 /* the retuned kinds' coefficient look-ahead (below, "coefficient look-ahead"); 0: every lane retunes for itself (round 5's code, for A/B builds) */
-#endif
+/* (Compile-time switches for the look-ahead tables that were measured and lost — the amplitude envelope's value in the table entries, a
+   frame loop of its own for the table frames in more bodies than below, builds without the look-aheads — are described in docs/HISTORY.md.) */
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 // Which entry of the kind-sorted workgroup list (cheapest base kind first) workgroup blockIdx.x of a launch takes: from the END.
@@ -421,26 +404,24 @@ struct CoefTab {
     for (uint32_t k = 0; k < sizeof(T) / 4; ++k) w[k] = t.w[k];
   }
 };
-// The layout of a kind's entries: [coefficients][LFO: `mod` (f64, smooth kinds) or the fp32 value][amplitude envelope's value (fp32)].
-// The amplitude value rides along where the entry stays within kMaxEntry (not the smooth-f64 kinds' f64-filter bodies: five workgroups'
-// tables and bus tiles fill a CU's 160 KiB of LDS to within 10 KiB).
+// The layout of a kind's entries: [coefficients][LFO: `mod` (f64, smooth kinds) or the fp32 value].
 template <bool F32, bool COEF, bool LFO, bool SMOOTH> struct TabLayout {
   static constexpr uint32_t kCoef = COEF ? (F32 ? (uint32_t)sizeof(Lp24CoefF) : (uint32_t)sizeof(Lp24CoefD)) : 0u;
   static constexpr uint32_t kModOff = kCoef;
   static constexpr uint32_t kLfo = LFO ? (SMOOTH ? 8u : 4u) : 0u;
-  static constexpr uint32_t kAmpOff = kCoef + kLfo;
-  static constexpr bool kAmp = COEF && GROOVE_AMP_IN_TABLE && kAmpOff + 4u <= CoefTab::kMaxEntry;
-  static constexpr uint32_t kRaw = (kAmpOff + (kAmp ? 4u : 0u) + 7u) & ~7u;
+  static constexpr uint32_t kRaw = (kCoef + kLfo + 7u) & ~7u;
   static constexpr uint32_t kStride = F32 && COEF && kRaw <= 32u ? 32u : kRaw; // (a power of two where it costs nothing)
   static_assert(kStride <= CoefTab::kMaxEntry && kCoef % 8 == 0, "entry layout"); // (stride 0: a kind without a table)
 };
 // Do the live lanes of this wave share the filter envelope's stage (-> tab)?  The LFO's phase (-> ltab)?  Then their description,
 // from the first live lane, in SGPRs.  tab / ltab: 0 / 1 the compiler KNOWS to be in an SGPR (readfirstlane).
 // cut: the coefficients follow the LFO (an LFO-swept cutoff in an F32 kind), not the filter envelope.
+// (aA .. ta are written by nobody since the amplitude envelope's value left the table entries, and stay: without them the bodies of the
+// four class-specialised kinds compile to other register assignments.)
 struct WaveUniform { float A, c1, c2, tf; float aA, a1, a2, ta; uint32_t lph_lo, lph_hi; uint32_t tab, ltab, cut; };
 __device__ __forceinline__ float lane_value(float x, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane)); }
 __device__ __forceinline__ bool same_bits(float a, float b) { return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b); }
-template <bool COEF, bool LFO, int LFO_MODE, int CL, bool AMP>
+template <bool COEF, bool LFO, int LFO_MODE, int CL>
 __device__ __forceinline__ WaveUniform wave_uniform(const WelshParams& p, const WelshState& s, const WelshScratch& sc, bool live, uint32_t look) {
   WaveUniform u{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u, 0u};
   const uint64_t mask = __ballot(live);
@@ -463,13 +444,6 @@ __device__ __forceinline__ WaveUniform wave_uniform(const WelshParams& p, const 
       // bit patterns, so that a NaN (never produced; a torn shadow record could hold anything, but shadows are not live) cannot fake agreement
       const bool same = same_bits(s.fil.A, u.A) && same_bits(sc.fc1, u.c1) && same_bits(sc.fc2, u.c2) && same_bits(sc.tf, u.tf);
       u.tab = (uint32_t)__builtin_amdgcn_readfirstlane(__ballot(live && !same) == 0 ? 1 : 0);
-    }
-    if constexpr (AMP) { // the entries carry the amplitude envelope's value: its stage must be shared as well
-      if (u.tab != 0u) {
-        u.aA = lane_value(s.amp.A, l0); u.a1 = lane_value(sc.ac1, l0); u.a2 = lane_value(sc.ac2, l0); u.ta = lane_value(sc.ta, l0);
-        const bool same = same_bits(s.amp.A, u.aA) && same_bits(sc.ac1, u.a1) && same_bits(sc.ac2, u.a2) && same_bits(sc.ta, u.ta);
-        u.tab = (uint32_t)__builtin_amdgcn_readfirstlane(__ballot(live && !same) == 0 ? 1 : 0);
-      }
     }
   }
   return u;
@@ -497,7 +471,6 @@ __device__ __forceinline__ void wave_tab_fill(const WelshParams& p, const Render
       const float t = lp24_t_from_pct(pct, rc, hi);
       if constexpr (F32) CoefTab::store_of_lane(j, Lay::kStride, 0, lp24_coeff_from_t(p.fc, t, hi));
       else CoefTab::store_of_lane(j, Lay::kStride, 0, lp24_coefd_from_t(p.fc, t, hi, (p.flags & WF_COEF_WIDE) != 0));
-      if constexpr (Lay::kAmp) CoefTab::store_of_lane(j, Lay::kStride, Lay::kAmpOff, env_shape(u.ta + (float)(k0 + j), u.aA, u.a1, u.a2));
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the wave's own reads below come after these writes
@@ -509,41 +482,45 @@ __device__ __forceinline__ void welsh_block(const WelshParams& p, WelshState& s,
                                             uint32_t frames, uint32_t n, uint32_t v, bool active,
                                             size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, uint32_t prow, const DiagWhere& dw = DiagWhere{nullptr, 0, 0, 0}) {
   WelshScratch sc = welsh_scratch_init(p, rc);
-  // Static cutoff + wave-uniform patch: the six f64 coefficients are the same in every lane and
-  // never change, so they ride in SGPRs (12 VGPRs back; f64 FMAs take one scalar operand).
-  if constexpr (UNIFORM && F32OK && LFO_MODE != LFO_F64) {
-    // F32OK: the copy of the block for workgroups whose patches carry WF_FILTER_F32 (the host builds workgroups that are uniform in
+  if constexpr (UNIFORM) {
+    // F32FILT: the copy of the block for workgroups whose patches carry WF_FILTER_F32 (the host builds workgroups that are uniform in
     // it and lists them in UniformArgs::wg_f32) — the same segmented block with the filter's recurrence in fp32 (dsp_core.h "fp32
     // recurrence"); the state goes back into the f64 fields of the record.  A function of its own per class triple, like the f64
     // copies: both forms in ONE function (a scalar branch per block) spilled 100 - 150 bytes per lane in their hot loops and gave
     // back two thirds of the gain (profiles/r05_f32_filter.log).
-    welsh_scratch_f32_begin(p, s, rc, sc);
-    if (!RETUNE) sc.coef_f = make_scalar(sc.coef_f);
-    constexpr bool COEF_LA = RETUNE && GROOVE_COEF_LOOKAHEAD;
-    constexpr bool LFO_LA = LFO_MODE != LFO_F64 && CL != LFO_UNUSED && GROOVE_LFO_LOOKAHEAD;
-    typedef TabLayout<true, COEF_LA, LFO_LA, LFO_MODE == LFO_F64_SMOOTH> Lay;
+    constexpr bool F32FILT = F32OK && LFO_MODE != LFO_F64;
+    // Static cutoff + wave-uniform patch: the six coefficients are the same in every lane and never change, so they ride in SGPRs
+    // (12 VGPRs back in the f64 form; f64 FMAs take one scalar operand).
+    if constexpr (F32FILT) {
+      welsh_scratch_f32_begin(p, s, rc, sc);
+      if (!RETUNE) sc.coef_f = make_scalar(sc.coef_f);
+    } else {
+      if (!RETUNE) sc.coef = make_scalar(sc.coef);
+    }
+    constexpr bool COEF_LA = RETUNE && LFO_MODE != LFO_F64; // (the exact-f64 kind keeps its own coefficient forms: resonance routing, lp24_coefd_from_fc)
+    constexpr bool LFO_LA = LFO_MODE != LFO_F64 && CL != LFO_UNUSED;
+    typedef TabLayout<F32FILT, COEF_LA, LFO_LA, LFO_MODE == LFO_F64_SMOOTH> Lay;
     WaveUniform fu{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u, 0u}; // this segment's look-aheads (fu.tab, fu.ltab are wave-uniform)
     run_frames_segmented<FUSED, FASTONLY && (COEF_LA || LFO_LA)>(
         frames, n, v, active, ch_stride, out, rows, prow,
-        [&](float& L, float& R) { welsh_frame<true, RETUNE, LFO_MODE, C1, C2, CL, false, REST, false, true>(p, s, rc, sc, L, R); },
+        [&](float& L, float& R) { welsh_frame<true, RETUNE, LFO_MODE, C1, C2, CL, false, REST, false, F32FILT>(p, s, rc, sc, L, R); },
         [&](bool& live) { const uint32_t k = welsh_segment_begin(p, s, live); welsh_segment_start_hoisted(s, sc); return k; },
         [&](bool live, uint32_t seg) {
           fu.tab = 0u; fu.ltab = 0u;
-          if constexpr (COEF_LA || LFO_LA) { if (FASTONLY || seg >= CoefTab::kMinSegment) fu = wave_uniform<COEF_LA, LFO_LA, LFO_MODE, CL, Lay::kAmp>(p, s, sc, live, rc.look); }
+          if constexpr (COEF_LA || LFO_LA) { if (FASTONLY || seg >= CoefTab::kMinSegment) fu = wave_uniform<COEF_LA, LFO_LA, LFO_MODE, CL>(p, s, sc, live, rc.look); }
           if constexpr (FASTONLY && (COEF_LA || LFO_LA)) { // the promise this copy was chosen on (welsh_wave_tables_up): counted if it does not hold
             if (!((!COEF_LA || fu.tab != 0u) && (!LFO_LA || fu.ltab != 0u)) && __ballot(live) != 0 && (threadIdx.x & 63u) == 0) diag_count_fast_table_miss(dw.diag);
           }
         },
-        [&](uint32_t k) { if constexpr (COEF_LA || LFO_LA) { if ((fu.tab | fu.ltab) != 0u && (k & (CoefTab::kFrames - 1)) == 0) wave_tab_fill<true, COEF_LA, LFO_LA, LFO_MODE, CL>(p, rc, fu, k); } },
+        [&](uint32_t k) { if constexpr (COEF_LA || LFO_LA) { if ((fu.tab | fu.ltab) != 0u && (k & (CoefTab::kFrames - 1)) == 0) wave_tab_fill<F32FILT, COEF_LA, LFO_LA, LFO_MODE, CL>(p, rc, fu, k); } },
         [&](uint32_t k, float& L, float& R) {
           uint32_t tab = 0u, ltab = 0u;
           double mod = 0.0;
-          float tamp = 0.0f;
           if constexpr (COEF_LA) {
             tab = fu.tab;
             if (tab != 0u) {
-              sc.coef_f = CoefTab::load<Lp24CoefF>(k & (CoefTab::kFrames - 1), Lay::kStride);
-              if constexpr (Lay::kAmp) tamp = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kAmpOff);
+              if constexpr (F32FILT) sc.coef_f = CoefTab::load<Lp24CoefF>(k & (CoefTab::kFrames - 1), Lay::kStride);
+              else sc.coef = CoefTab::load<Lp24CoefD>(k & (CoefTab::kFrames - 1), Lay::kStride);
             }
           }
           float tlfo = 0.0f;
@@ -552,90 +529,27 @@ __device__ __forceinline__ void welsh_block(const WelshParams& p, WelshState& s,
             if constexpr (LFO_MODE == LFO_F64_SMOOTH) { if (ltab != 0u) mod = CoefTab::load<double>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); }
             else { if (ltab != 0u && ((p.flags & WF_LFO_AMP) || tab == 0u)) tlfo = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); } // (a cutoff-only LFO is in the coefficients already)
           }
-          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, true, Lay::kAmp>(p, s, rc, sc, L, R, tab, ltab, mod, tlfo, tamp);
+          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, F32FILT>(p, s, rc, sc, L, R, tab, ltab, mod, tlfo);
         },
         [&]() { // fast(): every look-ahead of this kind is up.  (The F32 kinds' fp32-filter bodies only: in the others the second loop costs
-                // registers — 2 - 20 scratch accesses per frame in one loop or the other, and 0.3438 -> 0.3607 ms per block with it everywhere.)
-          if constexpr (!(COEF_LA || LFO_LA) || !GROOVE_FAST_TABLE_LOOP || !(LFO_MODE == LFO_F32 || (GROOVE_FAST_TABLE_LOOP >= 2 && CL != OSC_ANY))) return false;
+                // registers — 2 - 20 scratch accesses per frame in one loop or the other, and 0.3438 -> 0.3607 ms per block with it everywhere.
+                // The FAST copies, FASTONLY, run the table frames' loop alone in every body with a table.)
+          if constexpr (!(F32FILT && LFO_MODE == LFO_F32 && (COEF_LA || LFO_LA))) return false;
           else return __builtin_amdgcn_readfirstlane((int)((!COEF_LA || fu.tab != 0u) && (!LFO_LA || fu.ltab != 0u))) != 0;
         },
         [&](uint32_t k, float& L, float& R) {
           constexpr int TABS = (COEF_LA ? 1 : 0) | (LFO_LA ? 2 : 0);
           double mod = 0.0;
-          float tlfo = 0.0f, tamp = 0.0f;
-          if constexpr (COEF_LA) {
-            sc.coef_f = CoefTab::load<Lp24CoefF>(k & (CoefTab::kFrames - 1), Lay::kStride);
-            if constexpr (Lay::kAmp) tamp = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kAmpOff);
-          }
-          if constexpr (LFO_LA) {
-            if constexpr (LFO_MODE == LFO_F64_SMOOTH) mod = CoefTab::load<double>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff);
-            else { if (!COEF_LA || (p.flags & WF_LFO_AMP)) tlfo = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); }
-          }
-          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, true, Lay::kAmp, TABS>(p, s, rc, sc, L, R, 1u, 1u, mod, tlfo, tamp);
-        },
-        [&](uint32_t seg, bool live) {
-          welsh_segment_end_hoisted<CL == LFO_UNUSED>(p, s, seg, live);
-          if constexpr (COEF_LA) { if (fu.tab != 0u) { if (live) s.fil.value = env_last_value_of(s.fil); sc.prev_pct = __builtin_nanf(""); } }
-          if constexpr (LFO_LA) { if (fu.ltab != 0u && live) { s.lfo.phase += (uint64_t)seg * p.lfo_inc; if constexpr (LFO_MODE == LFO_F64_SMOOTH) welsh_lfo_reseed_smooth<CL>(p, s, sc); } }
-        },
-        [&](uint32_t f, uint32_t mine) { welsh_diag_zero(dw, s, active, f, mine); });
-    welsh_scratch_f32_end(s, sc);
-    return;
-  }
-  if (UNIFORM && !RETUNE) sc.coef = make_scalar(sc.coef);
-  if constexpr (UNIFORM) {
-    constexpr bool COEF_LA = RETUNE && LFO_MODE != LFO_F64 && GROOVE_COEF_LOOKAHEAD; // (the exact-f64 kind keeps its own coefficient forms: resonance routing, lp24_coefd_from_fc)
-    constexpr bool LFO_LA = LFO_MODE != LFO_F64 && CL != LFO_UNUSED && GROOVE_LFO_LOOKAHEAD;
-    typedef TabLayout<false, COEF_LA, LFO_LA, LFO_MODE == LFO_F64_SMOOTH> Lay;
-    WaveUniform fu{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u, 0u, 0u, 0u};
-    run_frames_segmented<FUSED, FASTONLY && (COEF_LA || LFO_LA)>(
-        frames, n, v, active, ch_stride, out, rows, prow,
-        [&](float& L, float& R) { welsh_frame<true, RETUNE, LFO_MODE, C1, C2, CL, false, REST>(p, s, rc, sc, L, R); },
-        [&](bool& live) { const uint32_t k = welsh_segment_begin(p, s, live); welsh_segment_start_hoisted(s, sc); return k; },
-        [&](bool live, uint32_t seg) {
-          fu.tab = 0u; fu.ltab = 0u;
-          if constexpr (COEF_LA || LFO_LA) { if (FASTONLY || seg >= CoefTab::kMinSegment) fu = wave_uniform<COEF_LA, LFO_LA, LFO_MODE, CL, Lay::kAmp>(p, s, sc, live, rc.look); }
-          if constexpr (FASTONLY && (COEF_LA || LFO_LA)) { // the promise this copy was chosen on (welsh_wave_tables_up): counted if it does not hold
-            if (!((!COEF_LA || fu.tab != 0u) && (!LFO_LA || fu.ltab != 0u)) && __ballot(live) != 0 && (threadIdx.x & 63u) == 0) diag_count_fast_table_miss(dw.diag);
-          }
-        },
-        [&](uint32_t k) { if constexpr (COEF_LA || LFO_LA) { if ((fu.tab | fu.ltab) != 0u && (k & (CoefTab::kFrames - 1)) == 0) wave_tab_fill<false, COEF_LA, LFO_LA, LFO_MODE, CL>(p, rc, fu, k); } },
-        [&](uint32_t k, float& L, float& R) {
-          uint32_t tab = 0u, ltab = 0u;
-          double mod = 0.0;
-          float tamp = 0.0f;
-          if constexpr (COEF_LA) {
-            tab = fu.tab;
-            if (tab != 0u) {
-              sc.coef = CoefTab::load<Lp24CoefD>(k & (CoefTab::kFrames - 1), Lay::kStride);
-              if constexpr (Lay::kAmp) tamp = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kAmpOff);
-            }
-          }
           float tlfo = 0.0f;
-          if constexpr (LFO_LA) {
-            ltab = fu.ltab;
-            if constexpr (LFO_MODE == LFO_F64_SMOOTH) { if (ltab != 0u) mod = CoefTab::load<double>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); }
-            else { if (ltab != 0u && ((p.flags & WF_LFO_AMP) || tab == 0u)) tlfo = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); } // (a cutoff-only LFO is in the coefficients already)
-          }
-          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, false, Lay::kAmp>(p, s, rc, sc, L, R, tab, ltab, mod, tlfo, tamp);
-        },
-        [&]() { // (the f64-filter bodies keep one loop: see the fp32-filter copy above)
-          if constexpr (!(COEF_LA || LFO_LA) || GROOVE_FAST_TABLE_LOOP < 3 || LFO_MODE != LFO_F32) return false;
-          else return __builtin_amdgcn_readfirstlane((int)((!COEF_LA || fu.tab != 0u) && (!LFO_LA || fu.ltab != 0u))) != 0;
-        },
-        [&](uint32_t k, float& L, float& R) {
-          constexpr int TABS = (COEF_LA ? 1 : 0) | (LFO_LA ? 2 : 0);
-          double mod = 0.0;
-          float tlfo = 0.0f, tamp = 0.0f;
           if constexpr (COEF_LA) {
-            sc.coef = CoefTab::load<Lp24CoefD>(k & (CoefTab::kFrames - 1), Lay::kStride);
-            if constexpr (Lay::kAmp) tamp = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kAmpOff);
+            if constexpr (F32FILT) sc.coef_f = CoefTab::load<Lp24CoefF>(k & (CoefTab::kFrames - 1), Lay::kStride);
+            else sc.coef = CoefTab::load<Lp24CoefD>(k & (CoefTab::kFrames - 1), Lay::kStride);
           }
           if constexpr (LFO_LA) {
             if constexpr (LFO_MODE == LFO_F64_SMOOTH) mod = CoefTab::load<double>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff);
             else { if (!COEF_LA || (p.flags & WF_LFO_AMP)) tlfo = CoefTab::load<float>(k & (CoefTab::kFrames - 1), Lay::kStride, Lay::kModOff); }
           }
-          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, false, Lay::kAmp, TABS>(p, s, rc, sc, L, R, 1u, 1u, mod, tlfo, tamp);
+          welsh_frame<false, RETUNE, LFO_MODE, C1, C2, CL, true, REST, true, F32FILT, TABS>(p, s, rc, sc, L, R, 1u, 1u, mod, tlfo);
         },
         [&](uint32_t seg, bool live) {
           welsh_segment_end_hoisted<CL == LFO_UNUSED>(p, s, seg, live);
@@ -643,6 +557,7 @@ __device__ __forceinline__ void welsh_block(const WelshParams& p, WelshState& s,
           if constexpr (LFO_LA) { if (fu.ltab != 0u && live) { s.lfo.phase += (uint64_t)seg * p.lfo_inc; if constexpr (LFO_MODE == LFO_F64_SMOOTH) welsh_lfo_reseed_smooth<CL>(p, s, sc); } }
         },
         [&](uint32_t f, uint32_t mine) { welsh_diag_zero(dw, s, active, f, mine); });
+    if constexpr (F32FILT) welsh_scratch_f32_end(s, sc);
   } else {
     run_frames<FUSED>(frames, n, v, active, ch_stride, out, rows, prow, [&](uint32_t f, float& L, float& R) {
       if (f == 0) welsh_frame<true, RETUNE, LFO_MODE, C1, C2, CL>(p, s, rc, sc, L, R);
@@ -923,7 +838,7 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_ANY) GROOVE_NO_TAIL_CALLS vo
 // blocks, so a wave whose live voices agree on the filter envelope's record, the LFO's phase and the first-tick flag when a block starts
 // will find them in agreement at every segment of the block.  With one hot loop per function the compiler keeps it in registers in every
 // body (the same loop beside the per-lane loop cost 2 - 20 scratch accesses a frame in the f64-filter and smooth-f64 bodies:
-// GROOVE_FAST_TABLE_LOOP): 57 - 110 instructions a frame where the shared loop's table path ran 130 - 170.  In one job, headline
+// docs/HISTORY.md): 57 - 110 instructions a frame where the shared loop's table path ran 130 - 170.  In one job, headline
 // 0.3301 - 0.3331 -> 0.3118 - 0.3172 ms per block, the library-proportioned bank 0.3376 -> 0.3293, the whole timeline 0.2751 -> 0.2628.  The
 // promise is a counted assertion (diag.h fast_table_misses, required to be 0 like zero_segments).
 #ifndef GROOVE_WAVES_MIX

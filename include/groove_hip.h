@@ -121,9 +121,8 @@ int groove_fx_allpass_stream(groove_ctx* ctx);
  * four wavefronts per 64 voices — envelopes + LFO, oscillators, cutoff tangent + coefficient quotients, filter + gains — pipelined
  * over the block's frames through LDS, so that a bank which cannot fill the chip with voices fills it with the parts of a voice's
  * frame (csrc/welsh_split.h).  Same results bit for bit as the serial kernels run without their LFO look-ahead (groove_set_look_ahead),
- * within 2e-6 of them with.  Default 1,024 (65,536 voices: one workgroup per CU; a two-role form of the same kernel for banks of up
- * to twice that is off by default since the serial kernels' FAST bodies outrun it: GROOVE_SPLIT2_MAX_WAVES=2048 in the environment
- * brings it back); 0 = never.  No reference counterpart. */
+ * within 2e-6 of them with.  Default 1,024 (65,536 voices: one workgroup per CU); larger banks take the all-kinds kernel; 0 = never.
+ * No reference counterpart. */
 int groove_set_split_max_waves(groove_ctx* ctx, uint32_t waves);
 uint32_t groove_split_max_waves(groove_ctx* ctx);
 /* HIP events on the ctx stream, for measurement (bench.py): create / record / elapsed. */

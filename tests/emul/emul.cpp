@@ -57,8 +57,8 @@ static void welsh_emul_segment_frame(const WelshParams& p, WelshState& s, const 
   if (retune) welsh_emul_segment_frame2<true>(p, s, rc, sc, mode, L, R); else welsh_emul_segment_frame2<false>(p, s, rc, sc, mode, L, R);
 }
 
-// The role-split kernel's frame (csrc/welsh_split.h), role by role with what travels between the roles through LDS on the
-// device: role A = welsh_frame_front -> {sum (NaN: silent), gain} and the cutoff percent (NaN: no retune); role B = the tangent of
+// The three-role split of a frame (the first form of csrc/welsh_split.h; the device runs the four-role one below), role by role with
+// what travels between the roles through LDS: role A = welsh_frame_front -> {sum (NaN: silent), gain} and the cutoff percent (NaN: no retune); role B = the tangent of
 // the cutoff, negated above SR/4 (NaN: coefficients stand); role C = coefficients from the tangent, the filter step, the gains.
 // `coef` is role C's running coefficient set (welsh_scratch_init's at the start of a block).
 template <bool FIRST, bool RETUNE, int MODE, bool SEG>
@@ -330,7 +330,7 @@ void emul_bank_render(void* h, uint32_t frames, float* out) {
     Lp24CoefD split_coef = sc.coef; // role C's coefficients: welsh_scratch_init's at the start of the block
     for (uint32_t f = 0; f < frames; ++f) {
       float L, R;
-      if (split) { // mirrors welsh_split_front_impl's walk (frame 0 checked, then hoisted segments) with roles B and C in line
+      if (split) { // mirrors the front role's walk (welsh_split4_ctl: frame 0 checked, then hoisted segments) with the other roles in line
         if (f == 0) welsh_emul_split_frame<true, false>(b->wp[v], b->ws[v], rc, sc, split_coef, retunes, mode, L, R);
         else {
           if (seg_left == 0) {

@@ -129,7 +129,8 @@ def test_segmented_and_checked_forms_are_bit_identical():
 
 @pytest.mark.parametrize("roles", [3, 4])
 def test_role_split_frame_is_the_serial_frame_bit_for_bit(roles):
-    """csrc/welsh_split.h gives a voice-wave's frame to three wavefronts: front -> {sum | NaN, gain} and the cutoff percent |
+    """csrc/welsh_split.h gives a voice-wave's frame to several wavefronts.  roles = 3 (its first form; the device now runs the
+    four-role one): front -> {sum | NaN, gain} and the cutoff percent |
     NaN; the cutoff's tangent, negated above SR/4 | NaN; coefficients from the tangent, filter step, gains.  The same device
     text walked role by role on the CPU (tests/emul/emul.cpp) must give the segmented serial form's bits — every patch of
     the table (all waveforms, routings, sync, static and retuned filters, cutoffs on both sides of SR/4), note-on, release,

@@ -1,4 +1,4 @@
-"""GPU: the role-split Welsh kernels (csrc/welsh_split.h — four wavefronts per 64 voices: envelopes + LFO / oscillators / cutoff tangent + coefficient quotients / filter +
+"""GPU: the role-split Welsh kernel (csrc/welsh_split.h — four wavefronts per 64 voices: envelopes + LFO / oscillators / cutoff tangent + coefficient quotients / filter +
 gains, pipelined over the block's frames through LDS) computes every quantity with the serial kernels' statements in their
 order: bus rows, voice blocks and the state record must be the serial kernels' BIT FOR BIT, for every patch of the
 synthetic table (every waveform class, LFO routing, sync, both filter modes), through note-on, note-off, release, the idle
@@ -118,8 +118,8 @@ def test_split_is_the_default_for_mid_size_banks(gpu_ctx):
     assert "split" in s.kernel_form(256, True) and "split" in s.kernel_form(256, False)
     assert "split" not in s.kernel_form(4, True)            # a handful of frames: nothing to pipeline
     s.destroy()
-    mid = E.WelshSynth(gpu_ctx, P.welsh_voices_grouped(80_000, 0)[0])   # above one twelve-wave workgroup per CU: the all-kinds serial kernel since the end of
-    assert "split" not in mid.kernel_form(256, True)                    # round 6 (its FAST bodies walk a block faster than the two-role form: groove_hip.hip split2_max_waves)
+    mid = E.WelshSynth(gpu_ctx, P.welsh_voices_grouped(80_000, 0)[0])   # above one sixteen-wave workgroup per CU: the all-kinds serial kernel (its FAST
+    assert "split" not in mid.kernel_form(256, True)                    # bodies walk a block faster than the two-role form did: docs/HISTORY.md)
     mid.destroy()
     big = E.WelshSynth(gpu_ctx, P.welsh_voices_grouped(200_000, 0)[0])  # a second round of workgroups would cost more than the split saves
     assert "split" not in big.kernel_form(256, True)
@@ -129,20 +129,12 @@ def test_split_is_the_default_for_mid_size_banks(gpu_ctx):
     small.destroy()
 
 
-@pytest.mark.parametrize("roles", [2, 3, 4])
-def test_every_role_count_equals_the_serial_kernels_bit_for_bit(oracle, roles):
-    """The two-role form (front + tangent | back; two workgroups of eight wavefronts per CU: banks of up to 131,072 voices in
-    one round), the three-role form (front | tangent | back) and the four-role form (envelopes + LFO | oscillators | tangent +
-    coefficient quotients | back; sixteen wavefronts per CU), each selected with GROOVE_SPLIT_ROLES in a context of its own:
-    bit-identical to the serial kernels, all three render forms."""
-    import os
+def test_the_four_role_kernel_equals_the_serial_kernels_bit_for_bit(oracle):
+    """The role-split kernel (envelopes + LFO | oscillators | tangent + coefficient quotients | back; sixteen wavefronts per CU),
+    in a context of its own: bit-identical to the serial kernels, all three render forms."""
     from groove_amd import entities as E
-    os.environ["GROOVE_SPLIT_ROLES"] = str(roles)
-    word = {2: "two", 3: "three", 4: "four"}[roles] + " wavefronts"
-    try:
-        ctx = E.Context(0)
-    finally:
-        os.environ.pop("GROOVE_SPLIT_ROLES")
+    word = "four wavefronts"
+    ctx = E.Context(0)
     try:
         ctx.look_ahead = 1   # (the module's docstring)
         for n in (3072, 200):

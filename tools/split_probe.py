@@ -37,12 +37,10 @@ def main():
     lib = L.load()
     synth, on, off = bank_of(ctx, ids, a.voices)
     print("kernel form:", synth.kernel_form(256, True))
-    form = synth.kernel_form(256, True)
-    roles = 4 if "four wavefronts" in form else 3 if "three wavefronts" in form else 2
     if a.no_probe:
         read = lambda out, reset: 0  # noqa: E731
     else:
-        read = getattr(lib, f"groove_debug_split_probe_read{roles}")
+        read = lib.groove_debug_split_probe_read
         read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     out = (C.c_ulonglong * 12)()
     bus = ctx.bus(256)
@@ -62,9 +60,8 @@ def main():
     v = np.array(list(out), dtype=np.float64).reshape(4, 3)
     p0 = P.welsh_patch(ids[0])
     desc = f"o1={p0.oscillator_1.waveform} o2={p0.oscillator_2.waveform} lfo={p0.lfo_waveform} route={p0.lfo_routing} env_end={p0.filter_cutoff_end:.1f}" if len(ids) == 1 else ""
-    print(f"{a.voices} voices, patches {a.patches}: {ms:.4f} ms per block ({'product' if a.no_probe else 'probe'} build), {roles} roles  {desc}")
-    names = ["ctl  ", "osc  ", "mid  ", "back "] if roles == 4 else ["front", "mid  ", "back ", ""]
-    for r, name in enumerate(names):
+    print(f"{a.voices} voices, patches {a.patches}: {ms:.4f} ms per block ({'product' if a.no_probe else 'probe'} build)  {desc}")
+    for r, name in enumerate(["ctl ", "osc ", "mid ", "back"]):
         if v[r, 2] == 0:
             continue
         busy, wait = v[r, 0] / v[r, 2] / a.blocks, v[r, 1] / v[r, 2] / a.blocks
