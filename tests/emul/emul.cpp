@@ -10,6 +10,7 @@ namespace groove { int groove_emul_f32_filter = 0; } // 0: the product's f64 rec
 #include "../../groove_amd/csrc/welsh_tp.h"
 #include <vector>
 #include <cstring>
+#include <cstddef>
 using namespace groove;
 
 struct EmulBank {
@@ -282,6 +283,12 @@ void emul_welsh_classify(const groove_welsh_params* p, uint32_t sr, uint32_t out
   welsh_body_classes(o, base, cl, c1, c2);
   out[0] = (uint32_t)base; out[1] = (uint32_t)cl; out[2] = (uint32_t)c1; out[3] = (uint32_t)c2;
   out[4] = welsh_filter_f32_ok(o, (double)sr) ? 1u : 0u; out[5] = o.flags;
+}
+// Where welsh_wave_tables_up (kernels.h) reads a voice's state: word offsets of amp, fil, lfo and vflags in WelshState, the words of an
+// EnvState and of the whole record (out[0..5]); the device keeps word k of voice v at state[k n + v] (soa_load), groove_bank_download_state too.
+void emul_welsh_state_words(uint32_t out[6]) {
+  out[0] = offsetof(WelshState, amp) / 4; out[1] = offsetof(WelshState, fil) / 4; out[2] = offsetof(WelshState, lfo) / 4;
+  out[3] = offsetof(WelshState, vflags) / 4; out[4] = sizeof(EnvState) / 4; out[5] = sizeof(WelshState) / 4;
 }
 double emul_filter_f32_error(const groove_welsh_params* p, uint32_t sr) { WelshCold c; return welsh_filter_f32_error(derive_welsh(*p, (double)sr, c), (double)sr); }
 void emul_set_segmented(void* h, int on) { ((EmulBank*)h)->segmented = on; }

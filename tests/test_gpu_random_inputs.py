@@ -18,6 +18,83 @@ def _level(want):
     return np.maximum(1.0, np.sqrt(np.mean(want ** 2, axis=(0, 1))))
 
 
+def _mix_forms(ctx, params, steps, looks=(3, 1)):
+    """The MIX kernel's two forms on the same inputs (pipeline_min_waves = 1): "mix, block" — generate_batch_values_async, the block-writing
+    MIX kernel, per voice [2][frames][n] at each look-ahead word of `looks` — and "mix" — the fused render_mix at look-ahead 3 (and 7 if
+    asked), bus [frames][2].  `steps`: per block (apply(bank), frames); apply hands the bank its events and controls.  At look-ahead 7
+    the FAST copies are counted block by block against what the voices' state says they must be (tests/mix_bodies.fast_waves_expected):
+    buses[(7, "fast")] = [(frames, counted, expected, the first voices of the live waves that took the FAST copy)] per block."""
+    from tests import mix_bodies as M
+    from groove_amd import entities as E
+    n, total = len(params), sum(fr for _, fr in steps)
+    ctx.time_parallel_max_voices, ctx.split_max_waves, ctx.pipeline_min_waves = 0, 0, 1
+    blocks, buses = {}, {}
+    try:
+        for look in looks:
+            ctx.look_ahead = look
+            s, blk = E.WelshSynth(ctx, params), ctx.block(n, 256)
+            assert "mix_kernel" in s.kernel_form(256, True)
+            out = []
+            for apply, fr in steps:
+                apply(s)
+                s.generate_batch_values_async(blk, fr)
+                out.append(blk.download(fr))
+            blocks[look] = np.concatenate(out, axis=1).astype(np.float64)
+            s.destroy(); blk.destroy()
+        for look in (3, 7) if 7 in looks else (3,):
+            ctx.look_ahead = look
+            s, bus = E.WelshSynth(ctx, params), ctx.bus(total)
+            groups = M.workgroups(params) if look == 7 else None
+            fast = []
+            at = 0
+            for apply, fr in steps:
+                apply(s)
+                if groups:
+                    state = s.download_state()   # (waits for the blocks before; the events land first, as they would in the render)
+                    before = ctx.debug_info()["fast_waves"]
+                s.render_mix(bus, fr, at_frame=at)
+                if groups:
+                    s.download_state()
+                    fast.append((fr, ctx.debug_info()["fast_waves"] - before) + M.fast_waves_expected(state, groups))
+                at += fr
+            buses[look] = bus.download().astype(np.float64)
+            buses[(look, "fast")] = fast
+            s.destroy(); bus.destroy()
+    finally:
+        ctx.look_ahead = 3
+    return blocks, buses
+
+
+def _check_mix_bus(bus, block, want, flagged, seed):
+    """"mix" against the oracle's bus — the per-voice bar added in quadrature over the voices, not divided by their number — and against
+    the float64 sum of "mix, block"'s voices: rounding of an fp32 sum (16 x 2^-24 sum |voice| per frame) where no voice's patch is flagged
+    fp32-safe (the fused kernel alone filters those in fp32), else the fp32 criterion's 2e-6 RMS per flagged voice on top."""
+    from tests import mix_bodies as M
+    want_bus, level = want.sum(axis=2).T, np.maximum(1.0, np.sqrt(np.mean(want ** 2, axis=(0, 1))))
+    err = float(np.sqrt(np.mean((bus - want_bus) ** 2)))
+    assert np.isfinite(bus).all() and err <= 1e-5 * float(np.sqrt(np.sum(level ** 2))), (seed, err)
+    blk_sum, blk_abs = block.sum(axis=2).T, np.abs(block).sum(axis=2).T
+    if flagged == 0:
+        assert M.sum_rounding_ok(bus, blk_sum, blk_abs), (seed, M.sum_rounding_c(bus, blk_sum, blk_abs))
+    else:
+        assert np.sqrt(np.mean((bus - blk_sum) ** 2)) <= M.F32_BAR * flagged + 16 * 2.0 ** -24 * float(blk_abs.max()), seed
+    return err
+
+
+def _flagged(params):
+    """Voices whose patch the host flags fp32-safe in kinds 0 - 3 (the fused kernels filter them in fp32)."""
+    from tests import mix_bodies as M
+    memo = {}
+    count = 0
+    for p in params:
+        k = bytes(p)
+        if k not in memo:
+            c = M.classify(p)
+            memo[k] = c[0] < 4 and c[4] == 1
+        count += memo[k]
+    return count
+
+
 def test_random_patches_every_kernel_form_against_the_oracle(gpu_ctx, oracle):
     """Patches DRAWN from a seed (groove_amd.patches.random_welsh_patch: every continuous parameter, every routing, instant attacks, zero
     sustains, cutoffs from 40 Hz to 20 kHz) instead of the 32 benchmark ones, eight per bank in runs of eight voices on random keys, 40 blocks
@@ -69,6 +146,13 @@ def test_random_patches_every_kernel_form_against_the_oracle(gpu_ctx, oracle):
                 s.destroy(); blk.destroy()
             assert np.array_equal(got["split"].view(np.uint32), got["any, lanes' LFO"].view(np.uint32)), seed
             assert np.abs(got["any"].astype(np.float64) - got["any, lanes' LFO"]).max() <= 2e-6 * max(1.0, float(np.abs(want).max())), seed
+            # the MIX kernel's forms: "mix, block" voice by voice (and at look-ahead 1 the bits of "split": the same body templates), "mix" on its bus
+            steps = [((lambda s, b=b: s.handle_midi_events(T.note_events_np(lanes, keys, b == 0)) if b in (0, off_at) else None), 256) for b in range(blocks)]
+            mblk, mbus = _mix_forms(gpu_ctx, params, steps)
+            rms = np.sqrt(np.mean((mblk[3] - want) ** 2, axis=(0, 1))) / _level(want)
+            assert np.isfinite(mblk[3]).all() and rms.max() <= 1e-5, (seed, "mix, block", int(np.argmax(rms)), float(rms.max()))
+            assert np.array_equal(mblk[1], got["split"]), (seed, float(np.abs(mblk[1] - got["split"]).max()))
+            _check_mix_bus(mbus[3], mblk[3], want, _flagged(params), seed)
     finally:
         gpu_ctx.time_parallel_max_voices, gpu_ctx.split_max_waves, gpu_ctx.pipeline_min_waves = old
         gpu_ctx.look_ahead = 3
@@ -139,6 +223,20 @@ def test_random_note_event_sequences_in_every_kernel_form(gpu_ctx, oracle):
             assert np.array_equal(outs["split"], outs["any, lanes' LFO"]), seed
             assert np.abs(outs["any"] - outs["any, lanes' LFO"]).max() <= 2e-6 * max(1.0, np.abs(outs["any"]).max()), seed
             assert np.abs(outs["tp"] - outs["any"]).max() <= 2e-6 * max(1.0, np.abs(outs["any"]).max()), seed
+            # the MIX kernel's forms under the drawn scripts, FAST copies included (look-ahead 7: counted; blocks of 1 and 37 frames)
+            steps = [((lambda s, evs=evs: s.handle_midi_events(T.note_events(evs)) if evs else None), fr) for evs, fr in zip(script, sizes)]
+            mblk, mbus = _mix_forms(gpu_ctx, params, steps, looks=(3, 1, 7))
+            rms = np.sqrt(np.mean((mblk[3] - want) ** 2, axis=(0, 1)))
+            over = np.flatnonzero(rms > 1e-5)
+            assert len(set(int(v) % 32 for v in over)) <= 1 and rms.max() <= 2e-4, (seed, "mix, block", int(np.argmax(rms)), float(rms.max()), over)
+            assert np.array_equal(mblk[1], outs["split"]), (seed, float(np.abs(mblk[1] - outs["split"]).max()))
+            _check_mix_bus(mbus[3], mblk[3], want, _flagged(params), seed)
+            assert np.array_equal(mbus[7], mbus[3]), seed   # (bit 2 of the word only turns the counting on)
+            fast = mbus[(7, "fast")]
+            assert all(c == e for _, c, e, _ in fast), (seed, [f[:3] for f in fast])
+            # ... which puts live voices in FAST copies, in blocks of 1 and of 37 frames among them
+            assert {1, 37} & {fr for fr in sizes} <= {fr for fr, _, _, live in fast if live}, (seed, [(f[0], len(f[3])) for f in fast])
+            assert sum(len(live) for *_, live in fast) > 0 and gpu_ctx.debug_info()["fast_table_misses"] == 0, seed
     finally:
         gpu_ctx.time_parallel_max_voices, gpu_ctx.split_max_waves, gpu_ctx.pipeline_min_waves = old
         gpu_ctx.look_ahead = 3
@@ -190,6 +288,7 @@ def test_random_controls_on_a_sounding_bank_in_every_kernel_form(gpu_ctx, oracle
             ob = oracle.Bank.welsh(params)
             want = play(ob.note_events, lambda i, v, voice: ob.set_param(i, v, voice), ob.render)
             assert np.sqrt(np.mean(want ** 2)) > 1e-2
+            outs = {}
             for form in ("tp", "any", "split", "per-kind"):
                 gpu_ctx.time_parallel_max_voices = old[0] if form == "tp" else 0
                 gpu_ctx.split_max_waves = (1 << 20) if form == "split" else 0
@@ -205,7 +304,25 @@ def test_random_controls_on_a_sounding_bank_in_every_kernel_form(gpu_ctx, oracle
                 rms = np.sqrt(np.mean((got - want) ** 2, axis=(0, 1)))
                 bus = np.sqrt(np.mean(((got - want).sum(axis=2) / n) ** 2))
                 assert np.isfinite(got).all() and rms.max() <= 2e-4 and bus <= 1e-5, (seed, form, int(np.argmax(rms)), float(rms.max()), float(bus))
+                outs[form] = got
                 s.destroy(); blk.destroy()
+            # the MIX kernel's forms given the same changes ("mix, block" to the bars above; "mix" on its bus)
+            def step(b):
+                def apply(s):
+                    if b == 0 or b == 22:
+                        s.handle_midi_events(T.note_events_np(lanes, keys, True))
+                    if b == 14:
+                        s.handle_midi_events(T.note_events_np(lanes, keys, False))
+                    for idx, v, voice in script[b]:
+                        s.control_set_param_by_index(idx, v, voice=voice)
+                return apply
+            mblk, mbus = _mix_forms(gpu_ctx, params, [(step(b), sizes[b]) for b in range(blocks)])
+            rms = np.sqrt(np.mean((mblk[3] - want) ** 2, axis=(0, 1)))
+            bus = np.sqrt(np.mean(((mblk[3] - want).sum(axis=2) / n) ** 2))
+            assert np.isfinite(mblk[3]).all() and rms.max() <= 2e-4 and bus <= 1e-5, (seed, "mix, block", int(np.argmax(rms)), float(rms.max()), float(bus))
+            assert np.array_equal(mblk[1], outs["split"]), (seed, float(np.abs(mblk[1] - outs["split"]).max()))
+            cutoff_moves = any(idx == T.CTL_WELSH_CUTOFF for changes in script for idx, _, _ in changes)
+            _check_mix_bus(mbus[3], mblk[3], want, n if cutoff_moves else _flagged(params), seed)
     finally:
         gpu_ctx.time_parallel_max_voices, gpu_ctx.split_max_waves, gpu_ctx.pipeline_min_waves = old
     assert gpu_ctx.debug_info()["zero_segments"] == 0
