@@ -233,7 +233,7 @@ struct groove_ctx {
   // carries them, behind the run).  deferred_ap: lane sums written on that stream that groove_mix_deferred has taken and the NEXT
   // all-pass launch (same stream: ordered) puts on their bus.
   int fx_ap_stream = -1;
-  struct { const float* rows = nullptr; float* bus = nullptr; uint32_t n_rows = 0, frames = 0; int accumulate = 0; } deferred_ap;
+  TpPrev deferred_ap;
   hipEvent_t ev_ap_run = nullptr, ev_ap_x = nullptr;
   bool seq_allpass = false;             // GROOVE_FX_SEQ_ALLPASS=1: the sequential all-pass kernel (A/B and bit-identity tests)
   bool chunked_allpass = false;         // GROOVE_FX_CHUNKED_ALLPASS=1: the chunk-parallel all-pass kernel instead of the direct one
@@ -258,7 +258,8 @@ struct groove_ctx {
   float* d_dpart[2] = {nullptr, nullptr};
   size_t dpart_cap[2] = {0, 0};
   int dpart_next = 0;
-  struct { const float* rows = nullptr; float* bus = nullptr; uint32_t n_rows = 0, frames = 0; int accumulate = 0; size_t owned_cap = 0; } deferred;
+  TpPrev deferred; // (all zero when nothing is pending: a launch takes it as its `prev` as it stands)
+  size_t deferred_owned_cap = 0;
   // groove_mix_deferred takes the block's row-sum buffer AWAY from the block (owned_cap != 0: the pending rows live in a buffer
   // nobody else can write) and hands the block one of these instead; a consumed buffer comes back here (deferred_taken)
   std::vector<std::pair<float*, size_t>> spare_sums;
@@ -442,7 +443,6 @@ int block_normalise(groove_block* blk) {
 // An effect's memory (IIR state, rings, parameter arrays) is touched by one stream at a time: the ctx stream, or — for the
 // stages groove_fx_chain_process_async runs behind a block's asynchronous render — that render's side stream.  ev_done
 // marks the end of its last side-stream use; the ctx stream waits for it before it touches the effect again.
-hipStream_t side_stream_of(groove_ctx* ctx, int k);
 // ev_done of an effect whose last side-stream use was not followed by a record of its own: the CURRENT end of that stream
 // (later than needed, never earlier: the stream runs in order)
 int fx_done_event(groove_fx* fx) {
@@ -862,13 +862,14 @@ int ensure_seg_buffer(groove_ctx* ctx, float** buf, size_t* cap, size_t seg_floa
 // bus[f][ch] (+)= column sums of partial[row][ch][frame] on the ctx stream (fixed order: segments of 64 rows, then the
 // segments in index order; a single segment's sums go straight to the bus).
 constexpr uint32_t kRowsPerSeg = 64;
+constexpr uint32_t reduce_segs(uint32_t rows) { return (rows + kRowsPerSeg - 1) / kRowsPerSeg; }
+constexpr size_t reduce_seg_floats(uint32_t rows, uint32_t frames) { return (size_t)reduce_segs(rows) * 2 * frames; } // what launch_reduce needs of seg_buf
 constexpr size_t kMaxSpareSums = 8; // lane-sum buffers groove_mix_deferred keeps for blocks to take (deferred_taken)
 // `done` (optional): an event that completes with the LAST kernel of the reduction — bound to that dispatch's own completion
 // signal (hipExtLaunchKernelGGL), not recorded behind it: a recorded event is a barrier packet of its own, ~5 us of the
 // stream's timeline (docs/STREAMS.md).
-void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_t frames, float* seg_buf, float* bus_dev, int accumulate, hipEvent_t done = nullptr);
-void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_t frames, float* seg_buf, float* bus_dev, int accumulate, hipEvent_t done) {
-  const uint32_t cols = 2 * frames, segs = (rows + kRowsPerSeg - 1) / kRowsPerSeg;
+void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_t frames, float* seg_buf, float* bus_dev, int accumulate, hipEvent_t done = nullptr) {
+  const uint32_t cols = 2 * frames, segs = reduce_segs(rows);
   const dim3 blk(kThreads);
   if (segs == 1) {
     if (done) hipExtLaunchKernelGGL(partial_rows_kernel, dim3(blocks_for(cols), 1), blk, 0, ctx->stream, nullptr, done, 0, partial, rows, cols, kRowsPerSeg, seg_buf, bus_dev, accumulate);
@@ -882,18 +883,17 @@ void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_
 // The pending rows have been handed to a launch (or to bus_flush's reduction): a buffer groove_mix_deferred took from a block is
 // a spare from now on (stream order protects it: whoever is given it next writes it behind that launch — DESIGN.md section 5).
 void deferred_taken(groove_ctx* ctx) {
-  if (ctx->deferred.rows && ctx->deferred.owned_cap) {
-    ctx->spare_sums.emplace_back(const_cast<float*>(ctx->deferred.rows), ctx->deferred.owned_cap);
+  if (ctx->deferred.rows && ctx->deferred_owned_cap) {
+    ctx->spare_sums.emplace_back(const_cast<float*>(ctx->deferred.rows), ctx->deferred_owned_cap);
     if (ctx->spare_sums.size() > kMaxSpareSums) { // (a rotation holds one spare per block in flight; beyond that the list only grows when blocks die)
       // the smallest goes; hipFree waits for the device, which is why this only happens past the cap
       auto it = std::min_element(ctx->spare_sums.begin(), ctx->spare_sums.end(), [](const auto& x, const auto& y) { return x.second < y.second; });
       if (it->first != ctx->deferred.rows) { (void)hipFree(it->first); ctx->spare_sums.erase(it); }
     }
   }
-  ctx->deferred.rows = nullptr;
-  ctx->deferred.owned_cap = 0;
+  ctx->deferred = TpPrev{};
+  ctx->deferred_owned_cap = 0;
 }
-void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_t frames, float* seg_buf, float* bus_dev, int accumulate, hipEvent_t done);
 // The pending reduction of a bank's last paced block onto its bus (ctx stream).  host_wait: the HOST waits for the block's render
 // kernels (they were submitted a whole call ago), so that the ctx stream carries no cross-queue wait; otherwise (flush points) the
 // ctx stream waits for them itself.
@@ -916,7 +916,6 @@ int paced_reduce(groove_bank* b, bool host_wait) {
   GHIP(ctx, hipGetLastError());
   return 0;
 }
-int bus_flush_deferred(groove_ctx* ctx);
 // ---- the all-pass stream (groove_set_fx_allpass_stream)
 static hipStream_t ap_stream(groove_ctx* ctx) { return side_stream_of(ctx, ctx->fx_ap_stream); }
 static int ap_events(groove_ctx* ctx) {
@@ -940,37 +939,37 @@ static int ap_follow(groove_ctx* ctx) {
   GHIP(ctx, hipStreamWaitEvent(ap_stream(ctx), ctx->ev_ap_run, 0));
   return 0;
 }
-void launch_reduce(groove_ctx* ctx, const float* partial, uint32_t rows, uint32_t frames, float* seg_buf, float* bus_dev, int accumulate, hipEvent_t done);
 // Lane sums that wait for the next all-pass launch and will not get one: the ctx stream reduces them itself, behind the kernel that
 // wrote them and ahead of whichever all-pass writes that buffer next.
 int bus_flush_ap(groove_ctx* ctx) {
   if (!ctx->deferred_ap.rows) return 0;
-  const auto d = ctx->deferred_ap;
-  ctx->deferred_ap.rows = nullptr;
+  const TpPrev d = ctx->deferred_ap;
+  ctx->deferred_ap = TpPrev{};
   if (ap_join(ctx)) return 1;
-  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, (size_t)((d.n_rows + kRowsPerSeg - 1) / kRowsPerSeg) * 2 * d.frames)) return 1;
+  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, reduce_seg_floats(d.n_rows, d.frames))) return 1;
   launch_reduce(ctx, d.rows, d.n_rows, d.frames, ctx->d_fseg, d.bus, d.accumulate, nullptr);
   if (hipGetLastError() != hipSuccess) return fail(ctx, "bus_flush: launch failed");
   return ap_follow(ctx);
 }
-int bus_flush(groove_ctx* ctx) {
-  if (bus_flush_deferred(ctx)) return 1;
-  if (bus_flush_ap(ctx)) return 1;
+int bus_flush_deferred(groove_ctx* ctx) {
+  if (!ctx->deferred.rows) return 0;
+  const TpPrev d = ctx->deferred;
+  deferred_taken(ctx);
+  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, reduce_seg_floats(d.n_rows, d.frames))) return 1;
+  launch_reduce(ctx, d.rows, d.n_rows, d.frames, ctx->d_fseg, d.bus, d.accumulate);
+  return hipGetLastError() == hipSuccess ? 0 : fail(ctx, "bus_flush: launch failed");
+}
+// Pending PACED reductions of any bank go onto their buses before a call of another form adds to a bus (include/groove_hip.h: "any
+// unpaced render or mix flushes them"): call order is the order of a bus's sums.
+static int flush_paced(groove_ctx* ctx) {
+  if (bus_flush_ap(ctx)) return 1; // (lane sums waiting on the all-pass stream: the order of a bus's sums is the order of the calls)
   while (!ctx->paced_order.empty()) // (call order: the order of the banks' sums on a bus)
     if (const int rc = paced_reduce(ctx->paced_order.front(), false)) return rc;
   return 0;
 }
-int bus_flush_deferred(groove_ctx* ctx) {
-  if (!ctx->deferred.rows) return 0;
-  const auto d = ctx->deferred;
-  deferred_taken(ctx);
-  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, (size_t)((d.n_rows + kRowsPerSeg - 1) / kRowsPerSeg) * 2 * d.frames)) return 1;
-  launch_reduce(ctx, d.rows, d.n_rows, d.frames, ctx->d_fseg, d.bus, d.accumulate);
-  return hipGetLastError() == hipSuccess ? 0 : fail(ctx, "bus_flush: launch failed");
-}
+int bus_flush(groove_ctx* ctx) { return bus_flush_deferred(ctx) ? 1 : flush_paced(ctx); }
 int reduce_rows(groove_ctx* ctx, const float* rows_dev, uint32_t rows, uint32_t frames, float* bus_dev, int accumulate, hipEvent_t done = nullptr) {
-  const uint32_t cols = 2 * frames, segs = (rows + kRowsPerSeg - 1) / kRowsPerSeg;
-  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, (size_t)segs * cols)) return 1;
+  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, reduce_seg_floats(rows, frames))) return 1;
   launch_reduce(ctx, rows_dev, rows, frames, ctx->d_fseg, bus_dev, accumulate, done);
   GHIP(ctx, hipGetLastError());
   return 0;
@@ -1267,7 +1266,7 @@ void groove_shutdown(groove_ctx* ctx) {
   if (ctx->d_fseg) (void)hipFree(ctx->d_fseg);
   if (ctx->d_i16) (void)hipFree(ctx->d_i16);
   if (ctx->d_diag) (void)hipFree(ctx->d_diag);
-  if (ctx->deferred.rows && ctx->deferred.owned_cap) (void)hipFree(const_cast<float*>(ctx->deferred.rows));
+  if (ctx->deferred.rows && ctx->deferred_owned_cap) (void)hipFree(const_cast<float*>(ctx->deferred.rows));
   for (auto& sp : ctx->spare_sums) (void)hipFree(sp.first);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   for (int i = 0; i < kSideStreams; ++i) {
@@ -1655,135 +1654,170 @@ static uint32_t tp_vpw(const groove_bank* b) { // voices per wavefront of the ti
   }
   return (b->kind == BANK_WELSH && b->tp_pairs && b->ctx->tp_vpw2_min_voices && b->n >= b->ctx->tp_vpw2_min_voices) ? 2u : 1u;
 }
-static void launch_tp(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, hipStream_t st, const groove_fx* head = nullptr,
-                      hipEvent_t done = nullptr /* completes with the kernel (bound to the dispatch: kernels.h launch_bound) */, const TpPrev* prev = nullptr,
-                      uint32_t sampler_vpw = 0 /* sampler only: voices per wavefront (0: the default rule) */) {
-  groove_ctx* ctx = b->ctx;
-  TpArgs a{b->d_params, b->d_state, out, rows, chs, render_consts_of(ctx), b->n, frames};
-  if (prev) a.prev = *prev;
-  if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; } // Welsh, block-writing form: the BiQuad head fused (welsh_tp.h)
-  if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
-  else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
-  else { a.full_coef = b->tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
+// ---- which kernel form a bank takes for a block, and the launches of each form
+// THE form decision: the entry points below, fused_rows, use_split and groove_bank_kernel_form all ask here.
+enum class Form {
+  TimeParallel,      // use_tp: one launch (welsh_tp.h), all three bank kinds
+  WelshPerLane,      // n_vwaves == 0 (every voice its own patch): the per-lane kernel over the physical lanes
+  WelshSmallUniform, // below the per-kind pipeline's threshold: all base kinds in one launch (launch_small_uniform)
+  WelshBigUniform,   // at or above it: the mix kernel and / or one kernel per base kind — several launches on several streams
+  FmSerial,          // one voice per lane
+  SamplerSerial,
+};
+static Form form_of(const groove_bank* b, uint32_t frames) {
+  if (use_tp(b, frames)) return Form::TimeParallel;
+  if (b->kind == BANK_FM) return Form::FmSerial;
+  if (b->kind == BANK_SAMPLER) return Form::SamplerSerial;
+  if (b->n_vwaves == 0) return Form::WelshPerLane;
+  return b->n_vwaves < b->ctx->pipeline_min_waves ? Form::WelshSmallUniform : Form::WelshBigUniform;
 }
-// rows of partial[][2][frames] a bank's fused render writes
-static uint32_t fused_rows(const groove_bank* b, uint32_t frames) {
-  if (use_tp(b, frames)) return b->kind == BANK_SAMPLER ? sampler_tp_workgroups(b->n) : b->kind == BANK_WELSH ? welsh_tp_grid(b->n, tp_vpw(b)) : welsh_tp_workgroups(b->n, tp_vpw(b));
-  return (b->kind == BANK_WELSH && b->n_vwaves) ? (b->n_vwaves + kWaves - 1) / kWaves : blocks_for(b->n);
+// rows of partial[][2][frames] a bank's fused render writes: one per workgroup of the form's launch(es)
+static uint32_t fused_rows(const groove_bank* b, Form form) {
+  switch (form) {
+    case Form::TimeParallel: return b->kind == BANK_SAMPLER ? sampler_tp_workgroups(b->n) : b->kind == BANK_WELSH ? welsh_tp_grid(b->n, tp_vpw(b)) : welsh_tp_workgroups(b->n, tp_vpw(b));
+    case Form::WelshSmallUniform: case Form::WelshBigUniform: return (b->n_vwaves + kWaves - 1) / kWaves;
+    default: return blocks_for(b->n);
+  }
 }
-// The one argument block of the wave-uniform Welsh kernels: workgroups [wg_off, wg_off + n_wgs) of the bank's kind-sorted list.
-static UniformArgs uniform_args(const groove_bank* b, float* out, float* rows, uint32_t wg_off, size_t chs, uint32_t frames, uint32_t n_wgs) {
-  UniformArgs a{b->d_waves, b->d_state, out, rows, b->d_wg_list + wg_off, b->d_wg_cls + wg_off, b->d_wg_f32 + wg_off, chs, render_consts_of(b->ctx), b->n_vwaves, b->n, frames, n_wgs};
+// A small-uniform bank's launch is role-split (welsh_split.h) when the bank is mid-size and the block long enough.
+static bool use_split(const groove_bank* b, Form form, uint32_t frames) {
+  return form == Form::WelshSmallUniform && b->n_vwaves <= b->ctx->split_max_waves && frames >= 2 * kSplitChunk;
+}
+// The one argument block of the wave-uniform Welsh kernels: entries [wg_off, wg_off + n_wgs) of the bank's workgroup lists.
+static UniformArgs uniform_args(const groove_bank* b, float* out, float* rows, size_t wg_off, size_t chs, uint32_t frames, uint32_t n_wgs) {
+  UniformArgs a{b->d_waves, b->d_state, out, rows, b->d_wg_list + wg_off, b->d_wg_cls + wg_off, b->d_wg_f32 + wg_off, chs, render_consts_of(b->ctx), b->n_vwaves, b->n, frames, n_wgs, TpPrev{}};
   a.diag = b->ctx->d_diag;
 #ifdef GROOVE_HEARTBEAT
   a.heartbeat = b->ctx->hb;
 #endif
   return a;
 }
-// A Welsh bank below the per-kind pipeline's threshold: ONE launch for all its workgroups — role-split (welsh_split.h) when the
-// bank is mid-size, for the workgroups of the four class-specialised base kinds (the workgroup list is sorted by kind: they
-// come first); the rest, or everything, through the all-kinds kernel.
-static bool use_split(const groove_bank* b, uint32_t frames) {
-  return b->kind == BANK_WELSH && b->n_vwaves && !use_tp(b, frames) && b->n_vwaves <= b->ctx->split_max_waves && frames >= 2 * kSplitChunk;
+// The pieces of a wave-uniform bank: the per-base-kind slices of its kind-sorted workgroup list (kernels.h, "Workgroup KINDS":
+// the four class-specialised base kinds first, n_spec workgroups in all, then the two exact-f64 ones) ...
+struct KindSlices { uint32_t count[kBaseKinds] = {}, offset[kBaseKinds] = {}, n_spec = 0; };
+static KindSlices kind_slices(const groove_bank* b) {
+  KindSlices p;
+  for (uint32_t base = 0, at = 0; base < (uint32_t)kBaseKinds; ++base) {
+    p.offset[base] = at;
+    for (int c = 0; c < kClassCombos; ++c) p.count[base] += b->wgs_of_kind[base * kClassCombos + c];
+    at += p.count[base];
+  }
+  p.n_spec = p.offset[4];
+  return p;
 }
-static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
-static void launch_small_uniform(groove_bank* b, const UniformArgs& a, hipStream_t st, bool fused, uint32_t frames, hipEvent_t done = nullptr /* bound to the last launch */) {
-  // the workgroup list is sorted by kind: the four class-specialised base kinds first, then the two exact-f64 ones
-  uint32_t n_spec = 0, n_f64[2] = {0, 0};
-  for (int k = 0; k < 4 * kClassCombos; ++k) n_spec += b->wgs_of_kind[k];
-  for (int k = 0; k < kClassCombos; ++k) { n_f64[0] += b->wgs_of_kind[4 * kClassCombos + k]; n_f64[1] += b->wgs_of_kind[5 * kClassCombos + k]; }
-  if (n_spec) {
+// One base kind's uniform Welsh kernel over `a`'s workgroups on stream `st`: every base kind has class-specialised bodies
+// (round 6: the two exact-f64 kinds too), one translation unit each (csrc/welsh_class.hip).
+static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr) {
+  typedef void (*Launcher)(const UniformArgs&, hipStream_t, bool, hipEvent_t);
+  static constexpr Launcher of_kind[kBaseKinds] = {launch_welsh_uniform_specialised<0>, launch_welsh_uniform_specialised<1>, launch_welsh_uniform_specialised<2>,
+                                                   launch_welsh_uniform_specialised<3>, launch_welsh_uniform_specialised<4>, launch_welsh_uniform_specialised<5>};
+  of_kind[k](a, st, fused, done);
+}
+static void launch_kind_slice(const groove_bank* b, const KindSlices& p, int k, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
+  launch_welsh_kind(k, uniform_args(b, out, rows, p.offset[k], chs, frames, p.count[k]), st, fused, done);
+}
+// ... and the three sections of the MIX kernel (kernels.h; round 6): the class-specialised workgroups in three launches, each over a
+// third of them — the section's entries of the striped copies of all four lists (welsh_upload_params).
+static void launch_mix_section(const groove_bank* b, int sec, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
+  const size_t o = b->wg_list_cap + b->mix_off[sec];
+  const UniformArgs a = uniform_args(b, out, rows, o, chs, frames, b->mix_cnt[sec]);
+  if (fused) launch_welsh_uniform_mix(a, b->d_wg_base + o, st, done);
+  else launch_welsh_uniform_mix_unfused(a, b->d_wg_base + o, st, done);
+}
+// A Welsh bank below the per-kind pipeline's threshold: ONE launch for the workgroups of the four class-specialised base kinds —
+// role-split when `split`, the all-kinds kernel otherwise.  `done` is bound to the last launch.
+static void launch_small_uniform(const groove_bank* b, const UniformArgs& a, hipStream_t st, bool fused, bool split, hipEvent_t done) {
+  const KindSlices p = kind_slices(b);
+  if (p.n_spec) {
     UniformArgs s = a;
-    s.n_wgs = n_spec;
-    const hipEvent_t d = (n_f64[0] || n_f64[1]) ? nullptr : done;
-    if (use_split(b, frames)) launch_welsh_split4(s, b->d_wg_base, st, fused, d);
+    s.n_wgs = p.n_spec;
+    const hipEvent_t d = (p.count[4] || p.count[5]) ? nullptr : done;
+    if (split) launch_welsh_split4(s, b->d_wg_base, st, fused, d);
     else if (fused) launch_welsh_uniform_any(s, b->d_wg_base, st, d);
     else launch_welsh_uniform_any_unfused(s, b->d_wg_base, st, d);
   }
   // exact-f64 LFO kinds (rare; their bodies need 133 VGPRs): the per-kind kernels, budgeted for them, behind it on the same stream
-  uint32_t at = n_spec;
-  for (int j = 0; j < 2; ++j) {
-    if (!n_f64[j]) continue;
+  for (int k = 4; k < kBaseKinds; ++k) {
+    if (!p.count[k]) continue;
     UniformArgs r = a;
     r.prev = TpPrev{}; // (the launch above carried the previous block's rows)
-    r.wg_list = a.wg_list + at; r.wg_cls = a.wg_cls + at; r.n_wgs = n_f64[j];
-    launch_welsh_kind(4 + j, r, st, fused, (j == 1 || !n_f64[1]) ? done : nullptr);
-    at += n_f64[j];
+    r.wg_list = a.wg_list + p.offset[k]; r.wg_cls = a.wg_cls + p.offset[k]; r.n_wgs = p.count[k];
+    launch_welsh_kind(k, r, st, fused, (k == 5 || !p.count[5]) ? done : nullptr);
   }
 }
-// One base kind's uniform Welsh kernel (kernels.h, "Workgroup KINDS") on stream `st`.
-static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  // every base kind has class-specialised bodies (round 6: the two exact-f64 kinds too), one translation unit each (csrc/welsh_class.hip)
-  switch (k) {
-    case 0: launch_welsh_uniform_specialised_0(a, st, fused, done); break;
-    case 1: launch_welsh_uniform_specialised_1(a, st, fused, done); break;
-    case 2: launch_welsh_uniform_specialised_2(a, st, fused, done); break;
-    case 3: launch_welsh_uniform_specialised_3(a, st, fused, done); break;
-    case 4: launch_welsh_uniform_specialised_4(a, st, fused, done); break;
-    default: launch_welsh_uniform_specialised_5(a, st, fused, done); break;
+// Every form but the big uniform one is ONE launch sequence on ONE stream, and this is where it is launched.  fused: `rows` =
+// partial rows only; otherwise `out` = the planar block and `rows` = its row sums (kernels.h run_frames), null for none.
+// `done` (optional) completes with the (last) kernel: bound to the dispatch (kernels.h launch_bound).  `prev`: the previous
+// deferred block's rows, for this launch to put on their bus (time-parallel and small uniform forms); `head`: a BiQuad effect
+// bank fused into the block-writing time-parallel Welsh kernel (welsh_tp.h); `sampler_vpw`: time-parallel sampler, voices per
+// wavefront (0: the default rule).
+static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused, size_t chs, float* out, float* rows, hipStream_t st, hipEvent_t done = nullptr,
+                          const TpPrev* prev = nullptr, const groove_fx* head = nullptr, uint32_t sampler_vpw = 0) {
+  const dim3 grid(form == Form::TimeParallel ? 0 : fused_rows(b, form)), blk(kThreads);
+  switch (form) {
+    case Form::TimeParallel: {
+      TpArgs a{b->d_params, b->d_state, out, rows, chs, render_consts_of(b->ctx), b->n, frames, TpPrev{}};
+      if (prev) a.prev = *prev;
+      if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
+      if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
+      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
+      else { a.full_coef = b->tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
+      break;
+    }
+    case Form::WelshSmallUniform: {
+      UniformArgs a = uniform_args(b, out, rows, 0, chs, frames, grid.x);
+      if (prev) a.prev = *prev;
+      launch_small_uniform(b, a, st, fused, use_split(b, form, frames), done);
+      break;
+    }
+    case Form::WelshPerLane:
+      if (fused) launch_bound(welsh_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, render_consts_of(b->ctx));
+      else launch_bound(welsh_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, render_consts_of(b->ctx));
+      break;
+    case Form::FmSerial:
+      if (fused) launch_bound(fm_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows);
+      else launch_bound(fm_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows);
+      break;
+    case Form::SamplerSerial:
+      if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+      else launch_bound(sampler_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+      break;
+    case Form::WelshBigUniform: break; // (the callers' own walks over kind_slices / launch_mix_section: their stream policies differ on purpose)
   }
 }
-// fused: `rows` = partial rows only.  Otherwise `out` = the planar block and `rows` = its row sums (kernels.h run_frames).
+// groove_bank_render and the non-pipelined groove_bank_render_mix: everything on the ctx stream, but for the big uniform form.
 static int launch_render(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows) {
   groove_ctx* ctx = b->ctx;
   b->ctx_touched = true;
-  const dim3 grid(blocks_for(b->n)), blk(kThreads);
-  if (use_tp(b, frames)) {
-    launch_tp(b, frames, fused, chs, out, rows, ctx->stream);
-  } else if (b->kind == BANK_WELSH) {
-    const RenderConsts rc = render_consts_of(ctx);
-    if (b->n_vwaves == 0) { // interleaved bank: per-lane kernel over the physical lanes
-      if (fused) hipLaunchKernelGGL(welsh_render_kernel<true>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows, rc);
-      else hipLaunchKernelGGL(welsh_render_kernel<false>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows, rc);
-    } else {
-      // One kernel per base kind present, all running concurrently: the most expensive kind goes
-      // out first on the ctx stream (list scheduling, longest first), the others on side streams
-      // forked from it, and the ctx stream joins them before the bus reduction.
-      if (b->n_vwaves < ctx->pipeline_min_waves) { // small bank: all base kinds in one launch (kernels.h)
-        const uint32_t wgs = (b->n_vwaves + kWaves - 1) / kWaves;
-        UniformArgs a = uniform_args(b, out, rows, 0, chs, frames, wgs);
-        launch_small_uniform(b, a, ctx->stream, fused, frames);
-        GHIP(ctx, hipGetLastError());
-        return 0;
+  const Form form = form_of(b, frames);
+  if (form == Form::WelshBigUniform) {
+    // One kernel per base kind present, all running concurrently: the most expensive kind goes
+    // out first on the ctx stream (list scheduling, longest first), the others on side streams
+    // forked from it, and the ctx stream joins them before the bus reduction.
+    const KindSlices p = kind_slices(b);
+    int present = 0;
+    for (uint32_t c : p.count) present += c ? 1 : 0;
+    if (present > 1) GHIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+    int side = 0;
+    bool first_kind = true;
+    for (int k = kBaseKinds - 1; k >= 0; --k) {
+      if (!p.count[k]) continue;
+      hipStream_t st = ctx->stream;
+      if (!first_kind) {
+        st = side_stream_of(ctx, side);
+        GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0));
       }
-      uint32_t count[kBaseKinds] = {}, offset[kBaseKinds] = {};
-      {
-        uint32_t at = 0;
-        for (int base = 0; base < kBaseKinds; ++base) {
-          offset[base] = at;
-          for (int c = 0; c < kClassCombos; ++c) count[base] += b->wgs_of_kind[base * kClassCombos + c];
-          at += count[base];
-        }
+      launch_kind_slice(b, p, k, fused, chs, out, rows, frames, st);
+      if (!first_kind) {
+        GHIP(ctx, hipEventRecord(ctx->ev_join[side], st));
+        GHIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[side], 0));
+        ++side;
       }
-      int present = 0;
-      for (uint32_t c : count) present += c ? 1 : 0;
-      if (present > 1) GHIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-      int side = 0;
-      bool first_kind = true;
-      for (int k = kBaseKinds - 1; k >= 0; --k) {
-        if (!count[k]) continue;
-        hipStream_t st = ctx->stream;
-        if (!first_kind) {
-          st = side_stream_of(ctx, side);
-          GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0));
-        }
-        UniformArgs a = uniform_args(b, out, rows, offset[k], chs, frames, count[k]);
-        launch_welsh_kind(k, a, st, fused);
-        if (!first_kind) {
-          GHIP(ctx, hipEventRecord(ctx->ev_join[side], st));
-          GHIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[side], 0));
-          ++side;
-        }
-        first_kind = false;
-        ctx->need_fork = true; // ctx-stream work the pipelined path's side streams must see
-      }
+      first_kind = false;
+      ctx->need_fork = true; // ctx-stream work the pipelined path's side streams must see
     }
-  } else if (b->kind == BANK_FM) {
-    if (fused) hipLaunchKernelGGL(fm_render_kernel<true>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows);
-    else hipLaunchKernelGGL(fm_render_kernel<false>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows);
   } else {
-    if (fused) hipLaunchKernelGGL(sampler_render_kernel<true>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows, b->d_pcm);
-    else hipLaunchKernelGGL(sampler_render_kernel<false>, grid, blk, 0, ctx->stream, b->d_params, b->d_state, b->n, frames, chs, out, rows, b->d_pcm);
+    launch_single(b, form, frames, fused, chs, out, rows, ctx->stream);
   }
   GHIP(ctx, hipGetLastError());
   return 0;
@@ -1799,7 +1833,7 @@ int groove_bank_render(groove_bank* b, uint32_t frames, groove_block* out) {
   if (ctx_join(ctx)) return 1; // the bank's state may still be in flight on the side streams (pipelined fused renders)
   b->side_mode = 0;
   out->ready_mask = 0; // joined above
-  const uint32_t rows_n = fused_rows(b, frames);
+  const uint32_t rows_n = fused_rows(b, form_of(b, frames));
   float* rows = block_sums(out, rows_n, frames);
   if (!rows) return 1;
   auto rendered = [&]() { out->sum_rows = rows_n; out->sum_frames = frames; out->sums_valid = true; return 0; };
@@ -1822,13 +1856,18 @@ static bool fx_is_biquad12(uint32_t kind) {
     default: return false;
   }
 }
+// A block's ev_free and ev_ready[], created on its first asynchronous use.
+static int block_events(groove_block* blk) {
+  if (blk->ev_free) return 0;
+  GHIP(blk->ctx, hipEventCreateWithFlags(&blk->ev_free, kSyncEventFlags));
+  for (int k = 0; k < kSideStreams; ++k) GHIP(blk->ctx, hipEventCreateWithFlags(&blk->ev_ready[k], kSyncEventFlags));
+  return 0;
+}
 // `head` (may be null): a 12 dB BiQuad effect bank to be applied to the block inside the render kernel — only honoured
 // (*head_fused = true) when the bank renders time-parallel and its lanes are in the caller's order.
 // `chained`: an effect chain follows on this block (groove_bank_render_chain_async), so the lane sums the render would leave are
 // never read — a time-parallel Welsh render then does not write them (2 MB per block for config #3's 4,096 voices).
-static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out, groove_fx* head, bool* head_fused, bool chained = false);
-int groove_bank_render_async(groove_bank* b, uint32_t frames, groove_block* out) { return render_async_impl(b, frames, out, nullptr, nullptr); }
-static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out, groove_fx* head, bool* head_fused, bool chained) {
+static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out, groove_fx* head, bool* head_fused, bool chained = false) {
   if (head_fused) *head_fused = false;
   if (!b || !out) return fail(nullptr, "groove_bank_render_async: NULL argument");
   groove_ctx* ctx = b->ctx;
@@ -1839,16 +1878,12 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
   if (flush_events(b, use_tp(b, frames))) return 1;
   const bool was_released = out->released;
   if (block_acquire(out)) return 1; // an earlier asynchronous render into the same block comes first
-  const bool tp = use_tp(b, frames);
-  const bool small_uniform = !tp && b->kind == BANK_WELSH && b->n_vwaves && b->n_vwaves < ctx->pipeline_min_waves;
-  const bool uniform = !tp && b->kind == BANK_WELSH && b->n_vwaves && !small_uniform; // one kernel per base kind
+  const Form form = form_of(b, frames);
+  const bool tp = form == Form::TimeParallel, uniform = form == Form::WelshBigUniform;
   if (bank_side_mode(b, uniform ? 1 : 2)) return 1;
-  if (!out->ev_free) {
-    GHIP(ctx, hipEventCreateWithFlags(&out->ev_free, kSyncEventFlags));
-    for (int k = 0; k < kSideStreams; ++k) GHIP(ctx, hipEventCreateWithFlags(&out->ev_ready[k], kSyncEventFlags));
-  }
+  if (block_events(out)) return 1;
   const size_t chs = (size_t)out->cap * out->n;
-  const uint32_t rows_n = fused_rows(b, frames);
+  const uint32_t rows_n = fused_rows(b, form);
   const bool no_sums = chained && tp && b->kind == BANK_WELSH;
   float* rows = no_sums ? nullptr : block_sums(out, rows_n, frames);
   if (!rows && !no_sums) return 1;
@@ -1862,7 +1897,6 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
   const bool free_recorded_now = !(was_released && !b->ctx_touched);
   if (free_recorded_now) GHIP(ctx, hipEventRecord(out->ev_free, ctx->stream));
   b->ctx_touched = false;
-  const dim3 blk(kThreads);
   uint32_t used = 0;
   auto begin = [&](int k) -> hipStream_t {
     hipStream_t st = side_stream_of(ctx, k);
@@ -1880,34 +1914,23 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
     ctx->side_busy[k] = true;
   };
   if (uniform) {
-    uint32_t at = 0;
-    uint32_t count[kBaseKinds] = {}, offset[kBaseKinds] = {};
-    for (int base = 0; base < kBaseKinds; ++base) {
-      offset[base] = at;
-      for (int c = 0; c < kClassCombos; ++c) count[base] += b->wgs_of_kind[base * kClassCombos + c];
-      at += count[base];
-    }
+    const KindSlices p = kind_slices(b);
     // the exact-f64 kinds keep their per-kind kernels, most expensive first; the other four take the MIX kernel (block-writing form: kernels.h)
     for (int k = kBaseKinds - 1; k >= 4; --k) {
-      if (!count[k]) continue;
+      if (!p.count[k]) continue;
       hipStream_t st = begin(k);
-      UniformArgs a = uniform_args(b, dst, rows, offset[k], chs, frames, count[k]);
-      launch_welsh_kind(k, a, st, false);
+      launch_kind_slice(b, p, k, false, chs, dst, rows, frames, st);
       end(k);
     }
     for (int sec = 2; sec >= 0; --sec) {
       if (!b->mix_cnt[sec]) continue;
       hipStream_t st = begin(sec);
-      UniformArgs a = uniform_args(b, dst, rows, 0, chs, frames, b->mix_cnt[sec]);
-      const size_t o = b->wg_list_cap + b->mix_off[sec];
-      a.wg_list = b->d_wg_list + o; a.wg_cls = b->d_wg_cls + o; a.wg_f32 = b->d_wg_f32 + o;
-      launch_welsh_uniform_mix_unfused(a, b->d_wg_base + o, st);
+      launch_mix_section(b, sec, false, chs, dst, rows, frames, st);
       end(sec);
     }
   } else {
     const int k = b->stream_slot;
     hipStream_t st = begin(k);
-    const dim3 grid(blocks_for(b->n));
     if (tp) {
       const bool fuse = head && b->kind == BANK_WELSH && !b->order && fx_is_biquad12(head->kind) && head->n == b->n && head->ctx == ctx;
       if (fuse) { // the effect's state moves to this side stream (fx_acquire_ctx)
@@ -1920,7 +1943,7 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
       }
       // the block's "ready" event completes with the render kernel itself (no record behind it)
       const bool bind = ctx->bind_events && b->kind == BANK_WELSH;
-      launch_tp(b, frames, false, chs, dst, rows, st, fuse ? head : nullptr, bind ? out->ev_ready[k] : nullptr);
+      launch_single(b, form, frames, false, chs, dst, rows, st, bind ? out->ev_ready[k] : nullptr, nullptr, fuse ? head : nullptr);
       if (fuse) { // the effect's last use ends with that kernel too: its own event is recorded when somebody asks (fx_done_event)
         if (bind) head->done_recorded = false;
         else { GHIP(ctx, hipEventRecord(head->ev_done, st)); head->done_recorded = true; }
@@ -1928,16 +1951,8 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
         *head_fused = true;
       }
       ready_bound = bind;
-    } else if (small_uniform) { // all base kinds in one launch
-      UniformArgs a = uniform_args(b, dst, rows, 0, chs, frames, fused_rows(b, frames));
-      launch_small_uniform(b, a, st, false, frames);
-    } else if (b->kind == BANK_WELSH) {
-      const RenderConsts rc = render_consts_of(ctx);
-      hipLaunchKernelGGL(welsh_render_kernel<false>, grid, blk, 0, st, b->d_params, b->d_state, b->n, frames, chs, dst, rows, rc);
-    } else if (b->kind == BANK_FM) {
-      hipLaunchKernelGGL(fm_render_kernel<false>, grid, blk, 0, st, b->d_params, b->d_state, b->n, frames, chs, dst, rows);
     } else {
-      hipLaunchKernelGGL(sampler_render_kernel<false>, grid, blk, 0, st, b->d_params, b->d_state, b->n, frames, chs, dst, rows, b->d_pcm);
+      launch_single(b, form, frames, false, chs, dst, rows, st);
     }
     end(k);
   }
@@ -1946,6 +1961,7 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+int groove_bank_render_async(groove_bank* b, uint32_t frames, groove_block* out) { return render_async_impl(b, frames, out, nullptr, nullptr); }
 int groove_block_release(groove_block* b) {
   if (!b) return fail(nullptr, "groove_block_release: block is NULL");
   groove_ctx* ctx = b->ctx;
@@ -1958,10 +1974,7 @@ int groove_block_release(groove_block* b) {
     return 0;
   }
   if (block_acquire(b)) return 1;
-  if (!b->ev_free) {
-    GHIP(ctx, hipEventCreateWithFlags(&b->ev_free, kSyncEventFlags));
-    for (int k = 0; k < kSideStreams; ++k) GHIP(ctx, hipEventCreateWithFlags(&b->ev_ready[k], kSyncEventFlags));
-  }
+  if (block_events(b)) return 1;
   if (!marked) GHIP(ctx, hipEventRecord(b->ev_free, ctx->stream));
   b->released = true;
   return 0;
@@ -1980,51 +1993,46 @@ int groove_block_acquire(groove_block* b) {
 // render of block b+2 waits for the reduction of block b.
 static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev, int accumulate, bool paced = false) {
   groove_ctx* ctx = b->ctx;
-  const bool tp = use_tp(b, frames);
-  const bool small_uniform = !tp && b->kind == BANK_WELSH && b->n_vwaves && b->n_vwaves < ctx->pipeline_min_waves && ctx->pipeline_min_waves > 1;
-  const bool uniform = !tp && b->kind == BANK_WELSH && b->n_vwaves && !small_uniform; // one kernel per base kind
-  const uint32_t rows = fused_rows(b, frames);
-  const uint32_t cols = 2 * frames, rows_per_seg = 64, segs = (rows + rows_per_seg - 1) / rows_per_seg;
+  const Form form = form_of(b, frames);
+  const bool uniform = form == Form::WelshBigUniform;
+  const uint32_t rows = fused_rows(b, form);
+  const size_t part_floats = (size_t)rows * 2 * frames, seg_floats = reduce_seg_floats(rows, frames);
   if (bank_side_mode(b, uniform ? 1 : 2)) return 1;
   const int slot = b->pipe_slot;
   b->pipe_slot ^= 1;
   if (b->paced.active && (!paced || b->paced.slot == slot)) // (an unpaced call, or the slot's rows still owed)
     if (const int rc = paced_reduce(b, false)) return rc;
-  if (b->pipe_part_cap[slot] < (size_t)rows * cols || b->pipe_seg_cap[slot] < (size_t)segs * cols) {
+  if (b->pipe_part_cap[slot] < part_floats || b->pipe_seg_cap[slot] < seg_floats) {
     if (b->paced.active) if (const int rc = paced_reduce(b, false)) return rc;
     if (ctx_join(ctx)) return 1;
     GHIP(ctx, ctx_wait(ctx));
     if (b->d_pipe_part[slot]) GHIP(ctx, hipFree(b->d_pipe_part[slot]));
-    GHIP(ctx, hipMalloc(&b->d_pipe_part[slot], (size_t)rows * cols * 4));
-    b->pipe_part_cap[slot] = (size_t)rows * cols;
-    if (ensure_seg_buffer(ctx, &b->d_pipe_seg[slot], &b->pipe_seg_cap[slot], (size_t)segs * cols)) return 1;
+    GHIP(ctx, hipMalloc(&b->d_pipe_part[slot], part_floats * 4));
+    b->pipe_part_cap[slot] = part_floats;
+    if (ensure_seg_buffer(ctx, &b->d_pipe_seg[slot], &b->pipe_seg_cap[slot], seg_floats)) return 1;
     b->reduce_recorded[slot] = false;
   }
   if (!b->ev_reduce_done[slot]) {
     GHIP(ctx, hipEventCreateWithFlags(&b->ev_reduce_done[slot], kSyncEventFlags));
     for (int k = 0; k < kSideStreams; ++k) GHIP(ctx, hipEventCreateWithFlags(&b->ev_render_done[k][slot], kSyncEventFlags));
   }
-  uint32_t count[kSideStreams] = {}, offset[kSideStreams] = {}; // per stream: Welsh base kinds first, then the bank streams
-  // The MIX kernel (kernels.h; round 6): the four class-specialised base kinds in three launches, one per kind stream, each over a
-  // third of their workgroups (every third entry of the kind-sorted list); the exact-f64 kinds keep their per-kind kernels.
+  // Which side streams carry a launch.  The MIX kernel (kernels.h; round 6): the four class-specialised base kinds in three launches,
+  // one per kind stream, each over a third of their workgroups (every third entry of the kind-sorted list); the exact-f64 kinds
+  // keep their per-kind kernels.
+  KindSlices p;
+  uint32_t launches = 0;
   if (uniform) {
-    for (uint32_t base = 0, at = 0; base < (uint32_t)kBaseKinds; ++base) {
-      offset[base] = at;
-      for (int c = 0; c < kClassCombos; ++c) count[base] += b->wgs_of_kind[base * kClassCombos + c];
-      at += count[base];
-    }
-    for (int sec = 0; sec < 3; ++sec) count[sec] = b->mix_cnt[sec]; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds
-    count[3] = 0;
-  } else {
-    count[b->stream_slot] = rows; // one kernel, on this bank's side stream (the loop below runs once)
+    p = kind_slices(b);
+    for (int sec = 0; sec < 3; ++sec) if (b->mix_cnt[sec]) launches |= 1u << sec; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds; 3: nothing
+    for (int k = 4; k < kBaseKinds; ++k) if (p.count[k]) launches |= 1u << k;
+  } else if (rows) {
+    launches = 1u << b->stream_slot; // one kernel, on this bank's side stream (the loop below runs once)
   }
   if (ctx->need_fork) { // side streams must see what the ctx stream did since the last join (note events, uploads)
     GHIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     for (bool& f : ctx->fork_pending) f = true;
     ctx->need_fork = false;
   }
-  const RenderConsts rc = render_consts_of(ctx);
-  const dim3 blk(kThreads);
   // paced: the HOST waits for the reduction that frees this slot's rows (two blocks back: long done), so that the waits below are
   // dropped when they are made and the render streams carry no wait packet (docs/STREAMS.md item 13)
   // (A deadline that passes here loses nothing either: the streams wait for that reduction themselves below — with a wait packet this
@@ -2039,7 +2047,7 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
   }
   uint32_t used = 0;
   for (int k = kSideStreams - 1; k >= 0; --k) { // most expensive Welsh kind first
-    if (!count[k]) continue;
+    if (!(launches & (1u << k))) continue;
     hipStream_t st = side_stream_of(ctx, k);
     used |= 1u << k;
     if (ctx->fork_pending[k]) { GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0)); ctx->fork_pending[k] = false; }
@@ -2047,26 +2055,10 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
     // the block's "render done" event completes with the render kernel itself (kernels.h launch_bound): no record packet between
     // this block's kernel and the next block's on the stream
     const hipEvent_t done = ctx->bind_events ? b->ev_render_done[k][slot] : nullptr;
-    if (uniform && k < 3) {
-      UniformArgs a = uniform_args(b, b->d_pipe_part[slot], b->d_pipe_part[slot], 0, 0, frames, count[k]);
-      const size_t o = b->wg_list_cap + b->mix_off[k]; // the section's entries of the striped copies (welsh_upload_params)
-      a.wg_list = b->d_wg_list + o; a.wg_cls = b->d_wg_cls + o; a.wg_f32 = b->d_wg_f32 + o;
-      launch_welsh_uniform_mix(a, b->d_wg_base + o, st, done);
-    } else if (uniform) {
-      UniformArgs a = uniform_args(b, b->d_pipe_part[slot], b->d_pipe_part[slot], offset[k], 0, frames, count[k]);
-      launch_welsh_kind(k, a, st, true, done);
-    } else if (tp) {
-      launch_tp(b, frames, true, 0, b->d_pipe_part[slot], b->d_pipe_part[slot], st, nullptr, done);
-    } else if (small_uniform) { // all base kinds in one launch on this bank's stream
-      UniformArgs a = uniform_args(b, b->d_pipe_part[slot], b->d_pipe_part[slot], 0, 0, frames, rows);
-      launch_small_uniform(b, a, st, true, frames, done);
-    } else if (b->kind == BANK_WELSH) {
-      launch_bound(welsh_render_kernel<true>, dim3(rows), blk, st, done, b->d_params, b->d_state, b->n, frames, (size_t)0, b->d_pipe_part[slot], b->d_pipe_part[slot], rc);
-    } else if (b->kind == BANK_FM) {
-      launch_bound(fm_render_kernel<true>, dim3(rows), blk, st, done, b->d_params, b->d_state, b->n, frames, (size_t)0, b->d_pipe_part[slot], b->d_pipe_part[slot]);
-    } else {
-      launch_bound(sampler_render_kernel<true>, dim3(rows), blk, st, done, b->d_params, b->d_state, b->n, frames, (size_t)0, b->d_pipe_part[slot], b->d_pipe_part[slot], (const float*)b->d_pcm);
-    }
+    float* part = b->d_pipe_part[slot];
+    if (uniform && k < 3) launch_mix_section(b, k, true, 0, part, part, frames, st, done);
+    else if (uniform) launch_kind_slice(b, p, k, true, 0, part, part, frames, st, done);
+    else launch_single(b, form, frames, true, 0, part, part, st, done);
     if (!done) GHIP(ctx, hipEventRecord(b->ev_render_done[k][slot], st));
     if (!paced) GHIP(ctx, hipStreamWaitEvent(ctx->stream, b->ev_render_done[k][slot], 0));
     ctx->side_busy[k] = true;
@@ -2111,21 +2103,21 @@ int groove_bank_render_mix_paced(groove_bank* b, uint32_t frames, float* bus_dev
 }
 // How many partial rows a bank's deferred render writes (0: the bank does not take a deferred form and goes through
 // groove_bank_render_mix), and for a sampler bank the voices-per-workgroup spread of that form.
-static uint32_t deferred_rows_of(groove_bank* b, uint32_t frames, uint32_t* svpw_out = nullptr) {
+static uint32_t deferred_rows_of(groove_bank* b, uint32_t frames, uint32_t* svpw_out = nullptr, Form* form_out = nullptr) {
   groove_ctx* ctx = b->ctx;
   if (svpw_out) *svpw_out = 0;
   if (ctx->pipeline_min_waves <= 1 || frames == 0 || frames > 4096) return 0;
-  if (!use_tp(b, frames)) { // the all-kinds / role-split kernel of a mid-size Welsh bank, its rows summed by the next block's launch
-    if (!(b->kind == BANK_WELSH && b->n_vwaves && b->n_vwaves < ctx->pipeline_min_waves)) return 0;
-    uint32_t n_spec = 0;
-    for (int k = 0; k < 4 * kClassCombos; ++k) n_spec += b->wgs_of_kind[k];
-    const uint32_t urows = fused_rows(b, frames);
-    return n_spec && urows <= 2048 ? urows : 0;
+  const Form form = form_of(b, frames);
+  if (form_out) *form_out = form;
+  if (form != Form::TimeParallel) { // the all-kinds / role-split kernel of a mid-size Welsh bank, its rows summed by the next block's launch
+    if (form != Form::WelshSmallUniform) return 0;
+    const uint32_t urows = fused_rows(b, form);
+    return kind_slices(b).n_spec && urows <= 2048 ? urows : 0;
   }
   uint32_t svpw = 0; // sampler: spread over more workgroups than the form with a reduction launch would (welsh_tp.h)
   if (b->kind == BANK_SAMPLER) { svpw = sampler_tp_vpw_deferred(b->n); if (sampler_tp_workgroups(b->n, svpw) > 512) svpw = 0; }
   // (up to 2,048 rows: the 512 columns' workgroups then take two to four batches of rows, a few us of a render that is long by then)
-  const uint32_t rows = svpw ? sampler_tp_workgroups(b->n, svpw) : fused_rows(b, frames);
+  const uint32_t rows = svpw ? sampler_tp_workgroups(b->n, svpw) : fused_rows(b, form);
   if (rows == 0 || rows > 2048 || frames > kTpMaxFrames) return 0;
   if (svpw_out) *svpw_out = svpw;
   return rows;
@@ -2149,14 +2141,6 @@ static int ensure_dpart(groove_ctx* ctx, size_t need, uint32_t frames) {
   }
   return 0;
 }
-// Pending PACED reductions of any bank go onto their buses before a call of another form adds to a bus (include/groove_hip.h: "any
-// unpaced render or mix flushes them"): call order is the order of a bus's sums.
-static int flush_paced(groove_ctx* ctx) {
-  if (bus_flush_ap(ctx)) return 1; // (lane sums waiting on the all-pass stream: the order of a bus's sums is the order of the calls)
-  while (!ctx->paced_order.empty())
-    if (const int rc = paced_reduce(ctx->paced_order.front(), false)) return rc;
-  return 0;
-}
 // Fused render + mix whose bus reduction is left to the bank's NEXT deferred render (welsh_tp.h, tp_reduce_prev) — or to
 // whatever waits for the ctx stream, records an event on it or touches a bus (bus_flush).  For banks that render time-parallel
 // on the ctx stream with at most 2,048 partial rows; anything else is groove_bank_render_mix.
@@ -2171,30 +2155,23 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
   // deferral, the next block's kernel summing the rows — when the launch that would carry them exists (some workgroup of the four
   // class-specialised kinds) and the rows are few enough (deferred_rows_of).
   uint32_t svpw = 0;
-  const uint32_t rows = deferred_rows_of(b, frames, &svpw);
+  Form form = Form::TimeParallel;
+  const uint32_t rows = deferred_rows_of(b, frames, &svpw, &form);
   if (rows == 0) return groove_bank_render_mix(b, frames, bus_dev, accumulate);
-  const bool tp = use_tp(b, frames);
   GHIP(ctx, hipSetDevice(ctx->device));
   if (const int rc = flush_paced(ctx)) return rc;
-  if (flush_events(b, tp)) return 1;
+  if (flush_events(b, form == Form::TimeParallel)) return 1;
   if (ctx_join(ctx)) return 1;
   const size_t need = (size_t)rows * 2 * frames;
   if (ensure_dpart(ctx, need, frames)) return 1;
   const int slot = ctx->dpart_next;
   ctx->dpart_next ^= 1;
-  TpPrev prev;
-  if (ctx->deferred.rows) { prev.rows = ctx->deferred.rows; prev.bus = ctx->deferred.bus; prev.n_rows = ctx->deferred.n_rows; prev.frames = ctx->deferred.frames; prev.accumulate = ctx->deferred.accumulate; }
+  const TpPrev prev = ctx->deferred;
   deferred_taken(ctx);
   b->ctx_touched = true;
-  if (!tp) {
-    UniformArgs a = uniform_args(b, ctx->d_dpart[slot], ctx->d_dpart[slot], 0, 0, frames, rows);
-    a.prev = prev;
-    launch_small_uniform(b, a, ctx->stream, true, frames);
-  } else {
-    launch_tp(b, frames, true, 0, ctx->d_dpart[slot], ctx->d_dpart[slot], ctx->stream, nullptr, nullptr, prev.rows ? &prev : nullptr, svpw);
-  }
+  launch_single(b, form, frames, true, 0, ctx->d_dpart[slot], ctx->d_dpart[slot], ctx->stream, nullptr, prev.rows ? &prev : nullptr, nullptr, svpw);
   GHIP(ctx, hipGetLastError());
-  ctx->deferred.rows = ctx->d_dpart[slot]; ctx->deferred.bus = bus_dev; ctx->deferred.n_rows = rows; ctx->deferred.frames = frames; ctx->deferred.accumulate = accumulate;
+  ctx->deferred = TpPrev{ctx->d_dpart[slot], bus_dev, rows, frames, accumulate};
   return 0;
 }
 // groove_bank_render_mix_deferred for SEVERAL small banks of different kinds at once: ONE launch for the whole block (welsh_tp.h
@@ -2247,7 +2224,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
   if (ensure_dpart(ctx, (size_t)grid * 2 * frames, frames)) return 1;
   const int slot = ctx->dpart_next;
   ctx->dpart_next ^= 1;
-  if (ctx->deferred.rows) { m.prev.rows = ctx->deferred.rows; m.prev.bus = ctx->deferred.bus; m.prev.n_rows = ctx->deferred.n_rows; m.prev.frames = ctx->deferred.frames; m.prev.accumulate = ctx->deferred.accumulate; }
+  m.prev = ctx->deferred;
   deferred_taken(ctx);
   m.rows = ctx->d_dpart[slot]; m.rc = render_consts_of(ctx); m.frames = frames;
   static const InlineEvents no_events{};
@@ -2255,7 +2232,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
   for (uint32_t i = 0; i < n_banks; ++i) banks[i]->ctx_touched = true;
   if (of_kind[2]) of_kind[2]->inline_ev.n = 0;
   GHIP(ctx, hipGetLastError());
-  ctx->deferred.rows = ctx->d_dpart[slot]; ctx->deferred.bus = bus_dev; ctx->deferred.n_rows = grid; ctx->deferred.frames = frames; ctx->deferred.accumulate = accumulate;
+  ctx->deferred = TpPrev{ctx->d_dpart[slot], bus_dev, grid, frames, accumulate};
   return 0;
 }
 int groove_bus_flush(groove_ctx* ctx) {
@@ -2279,19 +2256,19 @@ int groove_bank_render_mix(groove_bank* b, uint32_t frames, float* bus_dev, int 
   //  - in a project of several banks (synths, samplers) every bank takes it, so that the banks of one block
   //    run beside each other instead of one after the other (mixed-131072: 0.46 -> 0.2x ms per block).
   const bool force = ctx->pipeline_min_waves <= 1;
-  const bool big = b->kind == BANK_WELSH && b->n_vwaves >= ctx->pipeline_min_waves;
+  const Form form = form_of(b, frames);
+  // (a Welsh bank past the threshold that still renders time-parallel — the knobs can make one — has always walked this way too)
+  const bool big = form == Form::WelshBigUniform || (form == Form::TimeParallel && b->kind == BANK_WELSH && b->n_vwaves >= ctx->pipeline_min_waves);
   if (big || force || ctx->banks.size() > 1) return render_mix_pipelined(b, frames, bus_dev, accumulate);
   if (ctx_join(ctx)) return 1; // earlier pipelined blocks of this bank may still be running on the side streams
-  const uint32_t rows = fused_rows(b, frames);
-  const uint32_t cols = 2 * frames;
-  const uint32_t rows_per_seg = 64;
-  const uint32_t segs = (rows + rows_per_seg - 1) / rows_per_seg;
-  if (ctx->fpart_cap < (size_t)rows * cols) {
+  const uint32_t rows = fused_rows(b, form);
+  const size_t part_floats = (size_t)rows * 2 * frames;
+  if (ctx->fpart_cap < part_floats) {
     if (ctx->d_fpart) GHIP(ctx, hipFree(ctx->d_fpart));
-    GHIP(ctx, hipMalloc(&ctx->d_fpart, (size_t)rows * cols * 4));
-    ctx->fpart_cap = (size_t)rows * cols;
+    GHIP(ctx, hipMalloc(&ctx->d_fpart, part_floats * 4));
+    ctx->fpart_cap = part_floats;
   }
-  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, (size_t)segs * cols)) return 1;
+  if (ensure_seg_buffer(ctx, &ctx->d_fseg, &ctx->fseg_cap, reduce_seg_floats(rows, frames))) return 1;
   if (launch_render(b, frames, true, 0, ctx->d_fpart, ctx->d_fpart)) return 1;
   launch_reduce(ctx, ctx->d_fpart, rows, frames, ctx->d_fseg, bus_dev, accumulate);
   GHIP(ctx, hipGetLastError());
@@ -2299,16 +2276,21 @@ int groove_bank_render_mix(groove_bank* b, uint32_t frames, float* bus_dev, int 
 }
 const char* groove_bank_kernel_form(groove_bank* b, uint32_t frames, int fused) {
   if (!b) return "";
-  groove_ctx* ctx = b->ctx;
-  if (use_tp(b, frames)) return b->kind == BANK_WELSH ? (tp_vpw(b) == 2 ? "welsh_tp_kernel (time-parallel, two voices per wavefront)" : "welsh_tp_kernel (time-parallel, one wavefront per voice)") : b->kind == BANK_FM ? (tp_vpw(b) == 4 ? "fm_tp_kernel (time-parallel, four voices per wavefront)" : "fm_tp_kernel (time-parallel)") : "sampler_tp_kernel (time-parallel)";
-  if (b->kind == BANK_FM) return "fm_render_kernel (serial, one voice per lane)";
-  if (b->kind == BANK_SAMPLER) return "sampler_render_kernel (serial, one voice per lane)";
-  if (!b->n_vwaves) return "welsh_render_kernel (per-lane parameters)";
-  const bool pipelined = fused && (b->n_vwaves >= ctx->pipeline_min_waves || ctx->pipeline_min_waves <= 1);
-  if (b->n_vwaves >= ctx->pipeline_min_waves || (fused && ctx->pipeline_min_waves <= 1))
-    return pipelined ? "welsh_render_uniform_mix_kernel (big-bank form: three launches per block over thirds of the kind-sorted workgroups, one launch per base kind for the exact-f64 kinds only; class-specialised bodies, blocks pipelined)"
-                     : "welsh_render_uniform_kernel (one launch per base kind, class-specialised bodies)";
-  if (use_split(b, frames)) return "welsh_render_split4_kernel (role-split: four wavefronts per 64 voices, pipelined over the frames)";
+  const Form form = form_of(b, frames);
+  switch (form) {
+    case Form::TimeParallel:
+      if (b->kind == BANK_WELSH) return tp_vpw(b) == 2 ? "welsh_tp_kernel (time-parallel, two voices per wavefront)" : "welsh_tp_kernel (time-parallel, one wavefront per voice)";
+      if (b->kind == BANK_FM) return tp_vpw(b) == 4 ? "fm_tp_kernel (time-parallel, four voices per wavefront)" : "fm_tp_kernel (time-parallel)";
+      return "sampler_tp_kernel (time-parallel)";
+    case Form::FmSerial: return "fm_render_kernel (serial, one voice per lane)";
+    case Form::SamplerSerial: return "sampler_render_kernel (serial, one voice per lane)";
+    case Form::WelshPerLane: return "welsh_render_kernel (per-lane parameters)";
+    case Form::WelshBigUniform: // fused: groove_bank_render_mix takes render_mix_pipelined; otherwise groove_bank_render's walk (launch_render)
+      return fused ? "welsh_render_uniform_mix_kernel (big-bank form: three launches per block over thirds of the kind-sorted workgroups, one launch per base kind for the exact-f64 kinds only; class-specialised bodies, blocks pipelined)"
+                   : "welsh_render_uniform_kernel (one launch per base kind, class-specialised bodies)";
+    case Form::WelshSmallUniform: break;
+  }
+  if (use_split(b, form, frames)) return "welsh_render_split4_kernel (role-split: four wavefronts per 64 voices, pipelined over the frames)";
   return "welsh_render_uniform_any_kernel (all base kinds in one launch, class-specialised bodies)";
 }
 int groove_bank_reset(groove_bank* b) {
@@ -2493,7 +2475,7 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
   }
   a.frames = frames; a.wg_per_ch = wg_per_ch;
   if (ctx->deferred.rows && st == ctx->stream) { // groove_mix_deferred: this launch sums the pending block's rows onto its bus
-    a.prev.rows = ctx->deferred.rows; a.prev.bus = ctx->deferred.bus; a.prev.n_rows = ctx->deferred.n_rows; a.prev.frames = ctx->deferred.frames; a.prev.accumulate = ctx->deferred.accumulate;
+    a.prev = ctx->deferred;
     deferred_taken(ctx);
   }
   a.rows = (rv && direct) ? nullptr : rows;
@@ -2522,8 +2504,8 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
         GHIP(ctx, hipEventRecord(ctx->ev_ap_run, st));
         GHIP(ctx, hipStreamWaitEvent(ast, ctx->ev_ap_run, 0));
         if (ctx->deferred_ap.rows) { // the previous block's lane sums: written by that stream's last kernel, summed by this one
-          d.prev.rows = ctx->deferred_ap.rows; d.prev.bus = ctx->deferred_ap.bus; d.prev.n_rows = ctx->deferred_ap.n_rows; d.prev.frames = ctx->deferred_ap.frames; d.prev.accumulate = ctx->deferred_ap.accumulate;
-          ctx->deferred_ap.rows = nullptr;
+          d.prev = ctx->deferred_ap;
+          ctx->deferred_ap = TpPrev{};
         }
         if (V == 4) hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<4>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
         else hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<1>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
@@ -2810,7 +2792,7 @@ int groove_mix_deferred(groove_ctx* ctx, groove_block* blk, uint32_t frames, flo
     // writer without a wait; the ctx stream is not held up for the block).  Pending rows of any other kind go first, and the
     // all-pass stream behind them: the order of a bus's sums is the order of the calls.
     if (ctx->deferred.rows || ctx->deferred_ap.rows || !ctx->paced_order.empty()) { if (bus_flush(ctx) || ap_follow(ctx)) return 1; }
-    ctx->deferred_ap.rows = blk->d_sums_ap[blk->ap_flip]; ctx->deferred_ap.bus = bus_dev; ctx->deferred_ap.n_rows = blk->sum_rows; ctx->deferred_ap.frames = frames; ctx->deferred_ap.accumulate = accumulate;
+    ctx->deferred_ap = TpPrev{blk->d_sums_ap[blk->ap_flip], bus_dev, blk->sum_rows, frames, accumulate};
     blk->ap_flip ^= 1; // the block's next chain writes the other buffer: this one is read one launch from now
     blk->sums_valid = false; blk->sums_on_ap = false;
     return 0;
@@ -2818,15 +2800,15 @@ int groove_mix_deferred(groove_ctx* ctx, groove_block* blk, uint32_t frames, flo
   if (bus_flush(ctx)) return 1; // an earlier pending block nobody carried: its own reduction launch, first (order of the bus's sums)
   if (block_acquire(blk)) return 1;
   if (blk->sums_on_ap) { const int rc = groove_mix(ctx, &blk, 1, frames, bus_dev, accumulate); return rc; } // (not this path's buffers)
-  ctx->deferred.rows = blk->d_sums; ctx->deferred.bus = bus_dev; ctx->deferred.n_rows = blk->sum_rows; ctx->deferred.frames = frames; ctx->deferred.accumulate = accumulate;
+  ctx->deferred = TpPrev{blk->d_sums, bus_dev, blk->sum_rows, frames, accumulate};
   // the rows leave the block: whatever writes the block's lane sums next (its next render may run on another stream) cannot touch them
-  ctx->deferred.owned_cap = blk->sums_cap;
+  ctx->deferred_owned_cap = blk->sums_cap;
   blk->d_sums = nullptr; blk->sums_cap = 0; blk->sums_valid = false;
   // a spare at least as large as the buffer that left (a smaller one would make block_sums free and reallocate — device-wide
   // synchronisations inside the paced walk — until every buffer of the rotation had grown): the smallest that fits
   int pick = -1;
   for (int i = 0; i < (int)ctx->spare_sums.size(); ++i)
-    if (ctx->spare_sums[i].second >= ctx->deferred.owned_cap && (pick < 0 || ctx->spare_sums[i].second < ctx->spare_sums[pick].second)) pick = i;
+    if (ctx->spare_sums[i].second >= ctx->deferred_owned_cap && (pick < 0 || ctx->spare_sums[i].second < ctx->spare_sums[pick].second)) pick = i;
   if (pick >= 0) { blk->d_sums = ctx->spare_sums[pick].first; blk->sums_cap = ctx->spare_sums[pick].second; ctx->spare_sums.erase(ctx->spare_sums.begin() + pick); }
   return 0;
 }

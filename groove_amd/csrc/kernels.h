@@ -877,8 +877,8 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_MIX) GROOVE_NO_TAIL_CALLS vo
 }
 #endif // GROOVE_WELSH_MIX_TU
 static_assert(OSC_CLASSES == 5 && LFO_CLASSES == 6 && kClassCombos <= 256, "the class switch above lists 6 x 5 x 5 combinations, one byte each");
-// Launchers of the four class-specialised fused kernels, one translation unit each
-// (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..3) so that they compile in parallel.
+// Launchers of the class-specialised per-kind kernels, one translation unit each
+// (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5) so that they compile in parallel.
 // `done` (optional, every launcher below): an event that completes WITH the kernel — bound to the dispatch's own completion signal
 // (hipExtLaunchKernelGGL) instead of recorded behind it: a recorded event is a barrier packet of its own, ~5 us of its stream's timeline
 // before the next kernel of the stream starts.
@@ -887,12 +887,8 @@ static inline void launch_bound(K kernel, dim3 grid, dim3 blk, hipStream_t st, h
   if (done) hipExtLaunchKernelGGL(kernel, grid, blk, 0, st, nullptr, done, 0, args...);
   else hipLaunchKernelGGL(kernel, grid, blk, 0, st, args...);
 }
-void launch_welsh_uniform_specialised_0(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
-void launch_welsh_uniform_specialised_1(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
-void launch_welsh_uniform_specialised_2(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
-void launch_welsh_uniform_specialised_3(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr);
-void launch_welsh_uniform_specialised_4(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // exact-f64 LFO, static filter (round 6)
-void launch_welsh_uniform_specialised_5(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // exact-f64 LFO, retuned filter / resonance routing
+template <int BASE_KIND> // defined and instantiated by the base kind's translation unit (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5; 4, 5: the exact-f64 LFO kinds)
+void launch_welsh_uniform_specialised(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done);
 void launch_welsh_uniform_any(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done = nullptr); // fused: csrc/welsh_class.hip, -DGROOVE_BASE_KIND=9
 void launch_welsh_uniform_any_unfused(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done = nullptr); // writes the voice block: -DGROOVE_BASE_KIND=8
 void launch_welsh_uniform_mix(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done = nullptr); // the mix kernel, fused: -DGROOVE_BASE_KIND=10

@@ -1,4 +1,4 @@
-// welsh_class.hip — the fused, class-specialised uniform Welsh kernel of ONE base kind (compiled
+// welsh_class.hip — the class-specialised uniform Welsh kernel of ONE base kind and its launcher (compiled
 // with -DGROOVE_BASE_KIND=0..5, so the block bodies build in parallel), or (-DGROOVE_BASE_KIND=9)
 // the all-kinds kernel of small banks (=8: its block-writing form), or (=10 / 11) the mix kernel of big banks.  See
 // kernels.h, "Workgroup KINDS".
@@ -14,36 +14,16 @@
 #error "compile with -DGROOVE_BASE_KIND=<0..5, 8, 9, 10, 11>"
 #endif
 namespace groove {
-#if GROOVE_BASE_KIND == 0
-void launch_welsh_uniform_specialised_0(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F32, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F32, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
+#if GROOVE_BASE_KIND >= 0 && GROOVE_BASE_KIND < 6
+template <int BASE_KIND>
+void launch_welsh_uniform_specialised(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
+  constexpr int LFO_MODE = BASE_KIND < 2 ? LFO_F32 : BASE_KIND < 4 ? LFO_F64_SMOOTH : LFO_F64;
+  constexpr bool RETUNE = BASE_KIND % 2 == 1;
+  static_assert(wg_base_kind_of(LFO_MODE, RETUNE) == BASE_KIND, "base kind numbering");
+  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_MODE, RETUNE, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
+  else launch_bound(welsh_render_uniform_kernel<false, LFO_MODE, RETUNE, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
 }
-#elif GROOVE_BASE_KIND == 1
-void launch_welsh_uniform_specialised_1(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F32, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F32, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-}
-#elif GROOVE_BASE_KIND == 2
-void launch_welsh_uniform_specialised_2(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F64_SMOOTH, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F64_SMOOTH, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-}
-#elif GROOVE_BASE_KIND == 3
-void launch_welsh_uniform_specialised_3(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F64_SMOOTH, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F64_SMOOTH, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-}
-#elif GROOVE_BASE_KIND == 4
-void launch_welsh_uniform_specialised_4(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F64, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F64, false, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-}
-#elif GROOVE_BASE_KIND == 5
-void launch_welsh_uniform_specialised_5(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done) {
-  if (fused) launch_bound(welsh_render_uniform_kernel<true, LFO_F64, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-  else launch_bound(welsh_render_uniform_kernel<false, LFO_F64, true, true>, dim3(a.n_wgs), dim3(kThreads), st, done, a);
-}
+template void launch_welsh_uniform_specialised<GROOVE_BASE_KIND>(const UniformArgs&, hipStream_t, bool, hipEvent_t);
 #elif GROOVE_BASE_KIND == 9
 void launch_welsh_uniform_any(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done) {
   launch_bound(welsh_render_uniform_any_kernel<true>, dim3(a.n_wgs), dim3(kThreads), st, done, a, wg_base);
