@@ -22,6 +22,9 @@ FX_GAIN, FX_BITCRUSHER, FX_BIQUAD_LP12, FX_BIQUAD_LP24, FX_CHORUS, FX_DELAY, FX_
 # groove_control_index
 CTL_FX_CEILING, CTL_FX_BITS, CTL_FX_CUTOFF, CTL_FX_Q, CTL_FX_PASSBAND_RIPPLE, CTL_FX_ATTENUATION, CTL_FX_WET, CTL_FX_THRESHOLD = range(8)
 CTL_WELSH_DCA_GAIN, CTL_WELSH_DCA_PAN, CTL_WELSH_CUTOFF = 32, 33, 34
+# groove_ctl_source_kind, groove_ctl_law
+CTL_SRC_LFO, CTL_SRC_SIGNAL = range(2)
+CTL_LAW_BIPOLAR, CTL_LAW_AMPLITUDE, CTL_LAW_AMPLITUDE_INVERTED = range(3)
 
 
 class EnvelopeParams(C.Structure):
@@ -72,6 +75,21 @@ class FxParams(C.Structure):
         ("attenuation", C.c_float), ("reverb_seconds", C.c_float), ("wet", C.c_float),
         ("limit_min", C.c_float), ("limit_max", C.c_float), ("bandwidth_hz", C.c_float), ("db_gain", C.c_float),
     ]
+
+
+class CtlSource(C.Structure):
+    """groove_ctl_source: one source lane of a control link."""
+    _fields_ = [("source", C.c_uint32), ("waveform", C.c_uint32), ("duty", C.c_float), ("frequency_hz", C.c_double),
+                ("law", C.c_uint32)]
+
+
+def ctl_sources(n, **kw):
+    """n equal source lanes as a ctypes array (fields as in CtlSource; everything else zero)."""
+    arr = (CtlSource * n)()
+    for s in arr:
+        for k, v in kw.items():
+            setattr(s, k, v)
+    return arr
 
 
 def fx_params(**kw):

@@ -10,6 +10,7 @@
 #include "welsh_tp.h"
 #include "welsh_split.h"
 #include "fx_tp.h"
+#include "ctl_link.h"
 #include <dlfcn.h>
 #include <hip/hip_ext.h> // hipExtLaunchKernelGGL: an event bound to a kernel's own completion signal (launch_reduce, launch_welsh_tp)
 #include <rccl/rccl.h> // types, enumerators and prototypes only: the library itself is dlopen'ed (rccl_open)
@@ -175,6 +176,19 @@ struct groove_fx {
   bool done_recorded = true;    // false: the last use was a kernel whose end another event marks (a fused render's): ev_done is recorded on demand
 };
 
+// A controller linked to one parameter of an effect (groove_ctl_link_*; csrc/ctl_link.h).  Everything the apply kernel reads
+// lives on the device: the per-source-lane description (uploaded once, and again when the sample rate changes), the captured
+// samples and the flag that says there are any.
+struct groove_ctl_link {
+  groove_ctx* ctx;
+  uint32_t source, n_src, control_index;
+  groove_fx* target; // nullptr once the target has been destroyed (groove_fx_destroy clears it)
+  std::vector<groove_ctl_source> src;
+  uint64_t* d_lanes = nullptr; // delta64[n_src], duty64[n_src], then waveform[n_src], law[n_src] as uint32
+  float* d_value = nullptr;    // [n_src] captured samples (signal source)
+  uint32_t* d_captured = nullptr;
+};
+
 // Events that only order the library's own streams on one device: no timing, and no system-scope fence
 // (cache writeback + invalidate) when they are recorded — the host reads results through
 // hipMemcpy / hipStreamSynchronize, which fence by themselves.
@@ -249,6 +263,7 @@ struct groove_ctx {
   std::string err;
   std::vector<groove_bank*> banks;
   std::vector<groove_fx*> fxs;
+  std::vector<groove_ctl_link*> links;
   float* d_partial = nullptr;
   size_t partial_cap = 0;
   float* d_fpart = nullptr;  // fused path: partial[workgroup][2][frames]
@@ -1110,6 +1125,25 @@ int fx_check_uniform(groove_fx* fx) {
   return 0;
 }
 
+// ---- control links ----------------------------------------------------------------------
+// The device copy of a link's source lanes at the current sample rate (creation, groove_update_sample_rate: the caller has
+// waited for the ctx stream, or nothing has used the buffer yet).
+int ctl_upload_lanes(groove_ctl_link* l) {
+  groove_ctx* ctx = l->ctx;
+  const uint32_t n = l->n_src;
+  std::vector<uint64_t> w((size_t)3 * n);
+  uint32_t* u = reinterpret_cast<uint32_t*>(w.data() + (size_t)2 * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const groove_ctl_source& s = l->src[i];
+    w[i] = ctl_lfo_delta64(s.frequency_hz, (double)ctx->sr);
+    w[n + i] = ctl_lfo_duty64(s.waveform, s.duty);
+    u[i] = s.waveform;
+    u[n + i] = s.law;
+  }
+  GHIP(ctx, ctx_memcpy(ctx, l->d_lanes, w.data(), w.size() * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
 // ---- RCCL via dlopen -----------------------------------------------------------------
 // Function-pointer types are taken from the prototypes in <rccl/rccl.h>, so a change of the ABI is a
 // compile error here instead of a silently wrong call.
@@ -1257,6 +1291,7 @@ void groove_shutdown(groove_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)ctx_join(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  while (!ctx->links.empty()) groove_ctl_link_destroy(ctx->links.back());
   while (!ctx->banks.empty()) groove_bank_destroy(ctx->banks.back());
   while (!ctx->fxs.empty()) groove_fx_destroy(ctx->fxs.back());
   groove_comm_destroy(ctx);
@@ -1411,6 +1446,8 @@ int groove_update_sample_rate(groove_ctx* ctx, uint32_t hz) {
     if (fx_setup_state(fx)) return 1;
     if (fx_upload_params(fx)) return 1;
   }
+  for (groove_ctl_link* l : ctx->links) // an LFO's increment is f / SR
+    if (ctl_upload_lanes(l)) return 1;
   return 0;
 }
 int groove_event_create(groove_ctx* ctx, void** out_event) {
@@ -2364,6 +2401,8 @@ int groove_fx_destroy(groove_fx* fx) {
   if (fx->ev_done) (void)hipEventDestroy(fx->ev_done);
   auto it = std::find(ctx->fxs.begin(), ctx->fxs.end(), fx);
   if (it != ctx->fxs.end()) ctx->fxs.erase(it);
+  for (groove_ctl_link* l : ctx->links) // a link onto this effect has no target any more: its next apply is an error, not a write
+    if (l->target == fx) l->target = nullptr;
   (void)hipFree(fx->d_fa); (void)hipFree(fx->d_fb); (void)hipFree(fx->d_ua); (void)hipFree(fx->d_wet);
   (void)hipFree(fx->d_coef); (void)hipFree(fx->d_st); (void)hipFree(fx->d_ring); (void)hipFree(fx->d_tmp);
   delete fx;
@@ -2748,6 +2787,104 @@ int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, do
   if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
   GHIP(ctx, ctx_wait(ctx));
   return fx_upload_params(fx);
+}
+
+// ============================================================================ control links
+int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                           groove_ctl_link** out) {
+  if (!ctx || !src || !target || !out) return fail(ctx, "groove_ctl_link_create: NULL argument");
+  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_create: the target is not a live effect of this context");
+  if (n_src != 1 && n_src != target->n) return fail(ctx, "groove_ctl_link_create: n_src must be the target's lane count, or 1 (broadcast)");
+  switch (control_index) {
+    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE:
+      return fail(ctx, "groove_ctl_link_create: cutoff, q and passband-ripple become filter coefficients on the host (f64): not linkable on the device; use groove_fx_set_param");
+    case GROOVE_CTL_FX_WET:
+      return fail(ctx, "groove_ctl_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+    default:
+      if (!ctl_target_linkable(control_index)) return fail(ctx, "groove_ctl_link_create: unknown control index");
+  }
+  // the parameter has to be one the target's kernels read: the arrays are shared between kinds (groove_fx: d_fa)
+  const bool fits = (control_index == GROOVE_CTL_FX_CEILING && target->kind == GROOVE_FX_GAIN) ||
+                    (control_index == GROOVE_CTL_FX_BITS && target->kind == GROOVE_FX_BITCRUSHER) ||
+                    (control_index == GROOVE_CTL_FX_ATTENUATION && target->kind == GROOVE_FX_REVERB) ||
+                    (control_index == GROOVE_CTL_FX_THRESHOLD && (target->kind == GROOVE_FX_COMPRESSOR || target->kind == GROOVE_FX_LIMITER));
+  if (!fits) return fail(ctx, "groove_ctl_link_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
+  for (uint32_t i = 0; i < n_src; ++i) {
+    if (src[i].source != GROOVE_CTL_SRC_LFO && src[i].source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_create: unknown source kind");
+    if (src[i].source != src[0].source) return fail(ctx, "groove_ctl_link_create: the lanes of one link share one source kind");
+    if (src[i].source == GROOVE_CTL_SRC_LFO) {
+      if (!ctl_lfo_waveform_ok(src[i].waveform))
+        return fail(ctx, "groove_ctl_link_create: an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine (a noise generator's state at a block start has no closed form)");
+      if (!(src[i].frequency_hz >= 0.0) || !(src[i].frequency_hz < (double)ctx->sr)) return fail(ctx, "groove_ctl_link_create: LFO frequency outside [0, sample rate)");
+    } else if (!ctl_signal_law_ok(src[i].law)) {
+      return fail(ctx, "groove_ctl_link_create: unknown signal law");
+    }
+  }
+  GHIP(ctx, hipSetDevice(ctx->device));
+  groove_ctl_link* l = new groove_ctl_link();
+  l->ctx = ctx; l->source = src[0].source; l->n_src = n_src; l->control_index = control_index; l->target = target;
+  l->src.assign(src, src + n_src);
+  if (hipMalloc(&l->d_lanes, (size_t)3 * n_src * 8) != hipSuccess || hipMalloc(&l->d_value, (size_t)n_src * 4) != hipSuccess ||
+      hipMalloc(&l->d_captured, 4) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, "groove_ctl_link_create: hipMalloc failed");
+  }
+  if (hipMemsetAsync(l->d_value, 0, (size_t)n_src * 4, ctx->stream) != hipSuccess || hipMemsetAsync(l->d_captured, 0, 4, ctx->stream) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, "groove_ctl_link_create: hipMemsetAsync failed");
+  }
+  if (ctl_upload_lanes(l)) { groove_ctl_link_destroy(l); return 1; } // (its message stands)
+  ctx->links.push_back(l);
+  *out = l;
+  return 0;
+}
+int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t frames) {
+  if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
+  groove_ctx* ctx = l->ctx;
+  if (blk->ctx != ctx) return fail(ctx, "groove_ctl_link_capture: link and block belong to different contexts");
+  if (l->source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_capture: not a signal link");
+  if (blk->n != l->n_src) return fail(ctx, "groove_ctl_link_capture: block lanes != source lanes");
+  if (frames > blk->cap) return fail(ctx, "groove_ctl_link_capture: frames > block capacity");
+  if (frames == 0) return 0; // nothing has been transformed
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (block_acquire(blk) || block_normalise(blk)) return 1; // the source lanes are in the caller's order, like an effect's
+  hipLaunchKernelGGL(ctl_capture_kernel, dim3(blocks_for(blk->n)), dim3(kThreads), 0, ctx->stream, blk->d, (size_t)blk->cap * blk->n, blk->n, frames - 1,
+                     l->d_value, l->d_captured);
+  GHIP(ctx, hipGetLastError());
+  return 0;
+}
+int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
+  if (!l) return fail(nullptr, "groove_ctl_link_apply: link is NULL");
+  groove_ctx* ctx = l->ctx;
+  groove_fx* fx = l->target;
+  if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_apply: the target effect has been destroyed");
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
+  const uint32_t n = l->n_src;
+  const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + (size_t)2 * n);
+  const CtlLanes lanes{l->d_lanes, l->d_lanes + n, u, u + n};
+  const bool as_uint = ctl_target_is_uint(l->control_index);
+  hipLaunchKernelGGL(ctl_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
+                     as_uint ? nullptr : fx->d_fa, as_uint ? fx->d_ua : nullptr, fx->n);
+  GHIP(ctx, hipGetLastError());
+  return 0;
+}
+int groove_ctl_link_reset(groove_ctl_link* l) {
+  if (!l) return fail(nullptr, "groove_ctl_link_reset: link is NULL");
+  groove_ctx* ctx = l->ctx;
+  GHIP(ctx, hipSetDevice(ctx->device));
+  GHIP(ctx, hipMemsetAsync(l->d_captured, 0, 4, ctx->stream));
+  return 0;
+}
+int groove_ctl_link_destroy(groove_ctl_link* l) {
+  if (!l) return 0;
+  groove_ctx* ctx = l->ctx;
+  (void)hipStreamSynchronize(ctx->stream); // the link's kernels run there
+  auto it = std::find(ctx->links.begin(), ctx->links.end(), l);
+  if (it != ctx->links.end()) ctx->links.erase(it);
+  (void)hipFree(l->d_lanes); (void)hipFree(l->d_value); (void)hipFree(l->d_captured);
+  delete l;
+  return 0;
 }
 
 // ============================================================================ mix bus

@@ -418,3 +418,32 @@ class Effect:
         if self.h:
             self.ctx.L.groove_fx_destroy(self.h)
             self.h = None
+
+
+class ControlLink:
+    """A controller device linked to one parameter of an Effect, resident on the device (groove_ctl_link): IsController.work
+    once per block -> Controllable.control_set_param_by_index of the target, without a host wait.  `sources` is a ctypes array
+    of abi_types.CtlSource, one per target lane or one for all."""
+
+    def __init__(self, ctx, sources, target, control_index):
+        self.ctx, self.target, self.n_src = ctx, target, len(sources)
+        h = C.c_void_p()
+        _lib.check(ctx.L.groove_ctl_link_create(ctx.h, sources, len(sources), target.h, control_index, C.byref(h)), ctx.h)
+        self.h = h
+
+    def capture(self, block, frames=None):
+        """The signal passthrough's transform_audio: the block is only read; its last frame is kept for the next work()."""
+        frames = block.cap if frames is None else frames
+        _lib.check(self.ctx.L.groove_ctl_link_capture(self.h, block.h, frames), self.ctx.h)
+
+    def work(self, at_frame=0):
+        """groove_ctl_link_apply for the block that starts at_frame frames after the start."""
+        _lib.check(self.ctx.L.groove_ctl_link_apply(self.h, at_frame), self.ctx.h)
+
+    def reset(self):
+        _lib.check(self.ctx.L.groove_ctl_link_reset(self.h), self.ctx.h)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.L.groove_ctl_link_destroy(self.h)
+            self.h = None

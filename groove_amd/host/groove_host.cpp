@@ -1,6 +1,7 @@
 // groove_host.cpp — see groove_host.hpp.  Every audio operation goes through the C ABI of
 // libgroove_hip.so; there is no CPU audio path here.
 #include "groove_host.hpp"
+#include "../csrc/ctl_core.h" // the control links' value laws, for the links the host evaluates itself
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -72,13 +73,8 @@ void VoiceBankInstrument::note_off(uint8_t key, uint8_t velocity, uint64_t now) 
 }
 
 int VoiceBankInstrument::control_index_for_name(const std::string& name) const {
-  // #[derive(Control)] kebab-case names, nested fields joined with '-' (proc-macros/src/control.rs:127-131, 165): WelshSynth's `dca`
-  // field gives dca-gain / dca-pan; the filter's cutoff is the one Welsh voice parameter the reference's demos automate on effects
-  static const std::pair<const char*, int> table[] = {
-      {"dca-gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"dca-pan", GROOVE_CTL_WELSH_DCA_PAN}, {"pan", GROOVE_CTL_WELSH_DCA_PAN},
-      {"filter-cutoff", GROOVE_CTL_WELSH_CUTOFF}, {"cutoff", GROOVE_CTL_WELSH_CUTOFF}};
-  for (auto& t : table) if (name == t.first) return t.second;
-  return -1;
+  // #[derive(Control)] kebab-case names, nested fields joined with '-' (proc-macros/src/control.rs:127-131, 165)
+  return bank_control_index_for_name(name);
 }
 int VoiceBankInstrument::control_set_param(uint32_t index, double value01) {
   return groove_bank_set_param(bank_, GROOVE_ALL_VOICES, index, value01); // (fails, with the library's message, on a bank that has no such control)
@@ -94,7 +90,7 @@ ToyAudioSource::~ToyAudioSource() { if (block_) groove_block_destroy(block_); }
 int ToyAudioSource::tick(uint32_t) { return 0; } // the block already holds `level` everywhere
 
 // ------------------------------------------------------------------ FxEffect
-FxEffect::FxEffect(groove_ctx* ctx, uint32_t kind, const groove_fx_params* p, uint32_t lanes) : ctx_(ctx), lanes_(lanes) {
+FxEffect::FxEffect(groove_ctx* ctx, uint32_t kind, const groove_fx_params* p, uint32_t lanes) : ctx_(ctx), kind_(kind), lanes_(lanes) {
   groove_fx_create(ctx_, kind, p, lanes, &fx_);
 }
 FxEffect::~FxEffect() { if (fx_) groove_fx_destroy(fx_); }
@@ -107,13 +103,40 @@ int FxEffect::control_set_param(uint32_t index, double value01) {
   return groove_fx_set_param(fx_, GROOVE_ALL_VOICES, index, value01);
 }
 int FxEffect::control_index_for_name(const std::string& name) const {
-  // #[derive(Control)] kebab-case names (proc-macros/src/control.rs:127-131, 165)
-  static const std::pair<const char*, int> table[] = {
-      {"ceiling", GROOVE_CTL_FX_CEILING}, {"bits", GROOVE_CTL_FX_BITS}, {"bits-to-crush", GROOVE_CTL_FX_BITS},
-      {"cutoff", GROOVE_CTL_FX_CUTOFF}, {"q", GROOVE_CTL_FX_Q}, {"passband-ripple", GROOVE_CTL_FX_PASSBAND_RIPPLE},
-      {"attenuation", GROOVE_CTL_FX_ATTENUATION}, {"wet-dry-mix", GROOVE_CTL_FX_WET}, {"threshold", GROOVE_CTL_FX_THRESHOLD}};
-  for (auto& t : table) if (name == t.first) return t.second;
-  return -1;
+  return fx_control_index_for_name(name);
+}
+
+// ------------------------------------------------------------------ controller devices
+ControlSource::~ControlSource() {
+  for (Link& l : links_) if (l.dev) groove_ctl_link_destroy(l.dev);
+}
+void ControlSource::work_controls(Orchestrator& o, uint64_t at_frame) {
+  for (const Link& l : links_) {
+    if (l.dev) o.control_link(l.dev, at_frame);
+    else o.control_effect(l.target, l.index, host_value01(at_frame, o.sample_rate()));
+  }
+}
+void ControlSource::reset_controls() {
+  for (Link& l : links_) if (l.dev) groove_ctl_link_reset(l.dev);
+}
+void LfoController::work(uint64_t, uint64_t, std::vector<MidiEvent>&, Orchestrator& o) { work_controls(o, o.sequencing_frame()); }
+groove_ctl_source LfoController::source_desc() const {
+  groove_ctl_source s{};
+  s.source = GROOVE_CTL_SRC_LFO; s.waveform = waveform_; s.duty = duty_; s.frequency_hz = frequency_;
+  return s;
+}
+double LfoController::host_value01(uint64_t at_frame, uint32_t sample_rate) const {
+  return groove::ctl_lfo_value01_f64(waveform_, groove::ctl_lfo_delta64(frequency_, (double)sample_rate), groove::ctl_lfo_duty64(waveform_, duty_), at_frame);
+}
+int SignalPassthrough::transform_audio(groove_block* inout, uint32_t frames) {
+  for (const Link& l : links_)
+    if (l.dev && groove_ctl_link_capture(l.dev, inout, frames)) return 1;
+  return 0;
+}
+groove_ctl_source SignalPassthrough::source_desc() const {
+  groove_ctl_source s{};
+  s.source = GROOVE_CTL_SRC_SIGNAL; s.law = law_;
+  return s;
 }
 
 // ------------------------------------------------------------------ Sequencer / ControlTrip
@@ -376,7 +399,40 @@ uint64_t Orchestrator::performance_frames() const {
   const double beats = (double)end / MusicalTime::UNITS_IN_BEAT;
   return (uint64_t)std::ceil(beats * 60.0 / bpm_ * (double)sr_);
 }
-void Orchestrator::skip_to_start() { frames_ = 0; performing_ = true; ahead_primed_ = false; deferred_.clear(); }
+void Orchestrator::skip_to_start() {
+  frames_ = 0; performing_ = true; ahead_primed_ = false; deferred_.clear();
+  for (auto& n : nodes_)
+    if (n.entity && n.entity->control_source()) n.entity->control_source()->reset_controls();
+}
+int Orchestrator::link_control(Uid source, Uid target, const std::string& param) {
+  Entity* se = get(source);
+  ControlSource* src = se ? se->control_source() : nullptr;
+  if (!src) return fail("link_control: the source is not a controller device");
+  Entity* te = get(target);
+  if (!te || !(te->is_effect() || te->is_instrument())) return fail("link_control: the target is neither an effect nor an instrument");
+  const int idx = te->is_effect() ? static_cast<Effect*>(te)->control_index_for_name(param) : static_cast<Instrument*>(te)->control_index_for_name(param);
+  if (idx < 0) return fail("link_control: unknown control name " + param);
+  const groove_ctl_source desc = src->source_desc();
+  groove_fx* fx = te->is_effect() ? static_cast<Effect*>(te)->library_fx() : nullptr;
+  if (fx && fx_control_device_linkable(static_cast<FxEffect*>(te)->kind(), idx)) {
+    groove_ctl_link* link = nullptr;
+    if (groove_ctl_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link)) return fail(groove_last_error(ctx_));
+    src->add_link({link, target, (uint32_t)idx});
+    return 0;
+  }
+  if (desc.source == GROOVE_CTL_SRC_SIGNAL) {
+    err_ = "link_control: a signal source onto '" + param + "' would need a download per block (the host derives that parameter's device form); dropped";
+    return 2;
+  }
+  if (!groove::ctl_lfo_waveform_ok(desc.waveform)) return fail("link_control: an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine");
+  src->add_link({nullptr, target, (uint32_t)idx});
+  return 0;
+}
+int Orchestrator::control_link(groove_ctl_link* link, uint64_t at_frame) {
+  if (deferring_) { deferred_.push_back({0, 0, 0.0, link, at_frame}); return 0; }
+  if (groove_ctl_link_apply(link, at_frame)) return fail(groove_last_error(ctx_));
+  return 0;
+}
 int Orchestrator::control_effect(Uid target, uint32_t index, double value01) {
   Entity* e = get(target);
   if (e && e->is_instrument()) { // Controllable is generated for every entity (proc-macros/src/control.rs:171-183)
@@ -385,7 +441,7 @@ int Orchestrator::control_effect(Uid target, uint32_t index, double value01) {
     if (static_cast<Instrument*>(e)->control_set_param(index, value01)) return fail(groove_last_error(ctx_));
     return 0;
   }
-  if (deferring_) { deferred_.push_back({target, index, value01}); return 0; }
+  if (deferring_) { deferred_.push_back({target, index, value01, nullptr, 0}); return 0; }
   if (e && e->is_effect()) return static_cast<Effect*>(e)->control_set_param(index, value01);
   return 0;
 }
@@ -395,8 +451,12 @@ void Orchestrator::sequence_block(uint64_t at_frame, uint32_t frames) {
   uint64_t t1 = MusicalTime::frames_to_units(bpm_, sr_, at_frame + frames);
   if (t1 == t0) t1 = t0 + 1;
   std::vector<MidiEvent> midi;
-  for (auto& n : nodes_)
-    if (n.entity && n.entity->is_controller()) static_cast<Controller*>(n.entity.get())->work(t0, t1, midi, *this);
+  sequencing_frame_ = at_frame;
+  for (auto& n : nodes_) {
+    if (!n.entity) continue;
+    if (n.entity->is_controller()) static_cast<Controller*>(n.entity.get())->work(t0, t1, midi, *this);
+    else if (ControlSource* cs = n.entity->control_source()) cs->work_controls(*this, at_frame); // a signal passthrough: an effect that is worked too
+  }
   // broadcast_midi_messages (orchestrator.rs:710-754): every receiver on the channel
   for (const MidiEvent& m : midi) {
     auto range = midi_receivers_.equal_range(m.channel);
@@ -455,7 +515,9 @@ int Orchestrator::tick_ahead(StereoSample* out, uint32_t frames, uint32_t* ticks
     ahead_eval_ = false;
     if (rc) return 1;
     if (out && groove_download(ctx_, bus_, &out[0].l, (size_t)done * 2)) return fail(groove_last_error(ctx_));
-    for (const Deferred& d : deferred_) control_effect(d.target, d.index, d.value);
+    for (const Deferred& d : deferred_) {
+      if (d.link) control_link(d.link, d.at_frame); else control_effect(d.target, d.index, d.value);
+    }
     deferred_.clear();
     frames_ += done; // clock.tick_batch(ticks_completed)
   }
@@ -647,6 +709,16 @@ int gh_add_toy_instrument(void* h, double dca_gain, double dca_pan) {
 int gh_add_effect(void* h, uint32_t kind, const groove_fx_params* p) {
   Orchestrator* o = (Orchestrator*)h;
   return (int)o->add(std::unique_ptr<Entity>(new FxEffect(o->ctx(), kind, p, 1)));
+}
+// Controller devices and the `controls` links between them and a target's parameter (settings/src/controllers.rs:103-112).
+int gh_add_lfo_controller(void* h, uint32_t waveform, double duty, double frequency_hz) {
+  Orchestrator* o = (Orchestrator*)h;
+  if (!groove::ctl_lfo_waveform_ok(waveform)) { o->fail("gh_add_lfo_controller: an LFO is sine, triangle, square, sawtooth, pulse-width or triangle-sine"); return -1; }
+  return (int)o->add(std::unique_ptr<Entity>(new LfoController(waveform, (float)duty, frequency_hz)));
+}
+int gh_add_signal_passthrough(void* h) { return (int)((Orchestrator*)h)->add(std::unique_ptr<Entity>(new SignalPassthrough())); }
+int gh_link_control(void* h, int source_uid, int target_uid, const char* param_name) {
+  return ((Orchestrator*)h)->link_control((Uid)source_uid, (Uid)target_uid, param_name ? param_name : "");
 }
 int gh_patch(void* h, int source, int sink) { return ((Orchestrator*)h)->patch((Uid)source, (Uid)sink); }
 int gh_patch_chain_to_main_mixer(void* h, const int* uids, uint32_t n) {

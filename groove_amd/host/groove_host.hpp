@@ -55,6 +55,7 @@ struct MusicalTime {
 };
 
 class Orchestrator;
+class ControlSource;
 
 class Entity {
  public:
@@ -64,7 +65,35 @@ class Entity {
   virtual bool is_instrument() const { return false; }
   virtual bool is_effect() const { return false; }
   virtual bool is_controller() const { return false; }
+  // the source side of `controls` links, if the entity is a controller DEVICE (an LFO, a signal passthrough)
+  virtual ControlSource* control_source() { return nullptr; }
 };
+
+// #[derive(Control)] kebab-case names of the effects' parameters (proc-macros/src/control.rs:127-131, 165) -> groove_control_index; -1: none.
+inline int fx_control_index_for_name(const std::string& name) {
+  static const std::pair<const char*, int> table[] = {
+      {"ceiling", GROOVE_CTL_FX_CEILING}, {"bits", GROOVE_CTL_FX_BITS}, {"bits-to-crush", GROOVE_CTL_FX_BITS},
+      {"cutoff", GROOVE_CTL_FX_CUTOFF}, {"q", GROOVE_CTL_FX_Q}, {"passband-ripple", GROOVE_CTL_FX_PASSBAND_RIPPLE},
+      {"attenuation", GROOVE_CTL_FX_ATTENUATION}, {"wet-dry-mix", GROOVE_CTL_FX_WET}, {"threshold", GROOVE_CTL_FX_THRESHOLD}};
+  for (auto& t : table) if (name == t.first) return t.second;
+  return -1;
+}
+// The same for the controls the library's banks expose: WelshSynth's `dca` field gives dca-gain / dca-pan; the filter's cutoff is the one
+// Welsh voice parameter the reference's demos automate on effects.
+inline int bank_control_index_for_name(const std::string& name) {
+  static const std::pair<const char*, int> table[] = {
+      {"dca-gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"dca-pan", GROOVE_CTL_WELSH_DCA_PAN}, {"pan", GROOVE_CTL_WELSH_DCA_PAN},
+      {"filter-cutoff", GROOVE_CTL_WELSH_CUTOFF}, {"cutoff", GROOVE_CTL_WELSH_CUTOFF}};
+  for (auto& t : table) if (name == t.first) return t.second;
+  return -1;
+}
+// Can a control link onto this parameter of this kind of effect stay on the device (groove_ctl_link_create: the parameters whose device
+// form IS the value, on the kind whose kernels read them)?
+inline bool fx_control_device_linkable(uint32_t fx_kind, int index) {
+  return (index == GROOVE_CTL_FX_CEILING && fx_kind == GROOVE_FX_GAIN) || (index == GROOVE_CTL_FX_BITS && fx_kind == GROOVE_FX_BITCRUSHER) ||
+         (index == GROOVE_CTL_FX_ATTENUATION && fx_kind == GROOVE_FX_REVERB) ||
+         (index == GROOVE_CTL_FX_THRESHOLD && (fx_kind == GROOVE_FX_COMPRESSOR || fx_kind == GROOVE_FX_LIMITER));
+}
 
 // IsInstrument: Generates<StereoSample> + Ticks + HandlesMidi.
 class Instrument : public Entity {
@@ -189,9 +218,11 @@ class FxEffect : public Effect {
   groove_fx* library_fx() override { return fx_; }
   int control_set_param(uint32_t index, double value01) override;
   int control_index_for_name(const std::string& name) const override;
+  uint32_t kind() const { return kind_; }
  private:
   groove_ctx* ctx_;
   groove_fx* fx_ = nullptr;
+  uint32_t kind_;
   uint32_t lanes_;
 };
 
@@ -246,6 +277,55 @@ class ControlTrip : public Controller {
   double last_sent_ = -1.0;
 };
 
+// ---- controller devices ------------------------------------------------------------------------
+// The source side of the project's `controls` links (ControllerSettings, settings/src/controllers.rs:103-112): worked once per block,
+// before gather_audio, in the order the entities were added (handle_work, orchestrator.rs:631-708).  A link onto a parameter whose device
+// form is the value lives in the library (groove_ctl_link: no host wait); an LFO's link onto anything else goes through
+// Orchestrator::control_effect with the same law evaluated on the host in f64 (docs/DSP_SPEC.md section 13).
+class ControlSource {
+ public:
+  virtual ~ControlSource();
+  struct Link { groove_ctl_link* dev; Uid target; uint32_t index; }; // dev == nullptr: through Orchestrator::control_effect
+  virtual groove_ctl_source source_desc() const = 0;
+  void add_link(const Link& l) { links_.push_back(l); }
+  size_t links() const { return links_.size(); }
+  void work_controls(Orchestrator& o, uint64_t at_frame);
+  void reset_controls(); // Resets::reset: a signal source forgets what it captured
+ protected:
+  virtual double host_value01(uint64_t at_frame, uint32_t sample_rate) const { (void)at_frame; (void)sample_rate; return 0.0; }
+  std::vector<Link> links_;
+};
+
+// LfoController{waveform, frequency} (settings/src/controllers.rs:108-109).
+class LfoController : public Controller, public ControlSource {
+ public:
+  LfoController(uint32_t waveform, float duty, double frequency_hz) : waveform_(waveform), duty_(duty), frequency_(frequency_hz) {}
+  ControlSource* control_source() override { return this; }
+  void work(uint64_t start_units, uint64_t end_units, std::vector<MidiEvent>& out, Orchestrator& o) override;
+  bool is_finished(uint64_t) const override { return true; } // an LFO keeps no performance going
+  uint64_t end_units() const override { return 0; }
+  groove_ctl_source source_desc() const override;
+ protected:
+  double host_value01(uint64_t at_frame, uint32_t sample_rate) const override;
+ private:
+  uint32_t waveform_;
+  float duty_;
+  double frequency_;
+};
+
+// SignalPassthroughController (settings/src/controllers.rs:110-111): an effect that is the identity on its one lane (so that it can sit in
+// a patch cable), and a controller whose value is the last sample it has passed on — what a sidechain is built from.
+class SignalPassthrough : public Effect, public ControlSource {
+ public:
+  explicit SignalPassthrough(uint32_t law = GROOVE_CTL_LAW_BIPOLAR) : law_(law) {}
+  ControlSource* control_source() override { return this; }
+  uint32_t lanes() const override { return 1; }
+  int transform_audio(groove_block* inout, uint32_t frames) override; // the block is only read
+  groove_ctl_source source_desc() const override;
+ private:
+  uint32_t law_;
+};
+
 // ---- the orchestrator ----------------------------------------------------------------------
 class Orchestrator {
  public:
@@ -291,6 +371,14 @@ class Orchestrator {
   // ControlTrip -> effect parameter.  While the controllers are run one block ahead of the effects
   // the update is held back until the effects have processed the current block.
   int control_effect(Uid target, uint32_t index, double value01);
+  // Orchestrator::link_control (orchestrator.rs:1279-1294): `source` is a controller device, `param` one of the target's control names.
+  // 0: linked; 1: error; 2: dropped — a signal source onto a parameter only the host can derive would need a download per block
+  // (last_error() says so; the project loader turns it into a warning).
+  int link_control(Uid source, Uid target, const std::string& param);
+  // A device-resident link's value for the block at `at_frame`: applied now, or — like control_effect — held back while the controllers
+  // are run one block ahead of the effects.
+  int control_link(groove_ctl_link* link, uint64_t at_frame);
+  uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
 
@@ -335,8 +423,9 @@ class Orchestrator {
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block
   bool deferring_ = false;      // controllers are being run for the NEXT block
-  struct Deferred { Uid target; uint32_t index; double value; };
+  struct Deferred { Uid target; uint32_t index; double value; groove_ctl_link* link; uint64_t at_frame; }; // link set: a device-resident link's apply
   std::vector<Deferred> deferred_;
+  uint64_t sequencing_frame_ = 0;
 };
 
 // BusStation (src/mini/bus_station.rs:7-52): which track sends how much of its signal to which aux

@@ -304,7 +304,28 @@ ProjectDesc parse_project(const std::string& text, const std::string& assets_roo
       } else if (cls == "effect") {
         parse_effect(d.kind, body, d, p.warnings);
       } else if (cls == "controller") {
-        p.warnings.push_back("controller device '" + d.id + "' (" + d.kind + ") skipped: only tracks and trips drive this path");
+        // [midi, params] for the lfo, [midi] for the signal passthrough (controllers.rs:103-112: tuple variants)
+        ProjectDesc::ControllerDev c;
+        c.id = d.id; c.kind = d.kind;
+        const json5::Value* midi = body.is_array() && !body.arr.empty() && body.arr[0]->is_object() ? body.arr[0].get() : nullptr;
+        if (midi) { c.midi_in = (int)json5::to_int(midi->number_or("midi-in", 0), 0, 255, 0); c.midi_out = (int)json5::to_int(midi->number_or("midi-out", 0), 0, 255, 0); }
+        if (d.kind == "lfo") {
+          const json5::Value* params = body.is_array() && body.arr.size() >= 2 && body.arr[1]->is_object() ? body.arr[1].get() : nullptr;
+          if (!params) { p.warnings.push_back("malformed controller " + d.id); continue; }
+          parse_waveform(params->get("waveform"), c.waveform, c.duty);
+          c.frequency = params->number_or("frequency", 1.0);
+          const bool periodic = c.waveform == GROOVE_WAVE_SINE || c.waveform == GROOVE_WAVE_SQUARE || c.waveform == GROOVE_WAVE_PULSE_WIDTH ||
+                                c.waveform == GROOVE_WAVE_TRIANGLE || c.waveform == GROOVE_WAVE_SAWTOOTH || c.waveform == GROOVE_WAVE_TRIANGLE_SINE;
+          if (!periodic) { // (a noise generator's state at a block start has no closed form: docs/DSP_SPEC.md section 13)
+            p.warnings.push_back("lfo '" + d.id + "' skipped: its waveform is not one a block-rate LFO can be read from (noise, none and the debug waveforms)");
+            continue;
+          }
+          if (!(c.frequency >= 0.0)) { p.warnings.push_back("lfo '" + d.id + "' skipped: negative frequency"); continue; }
+        } else if (d.kind != "signal-passthrough-controller") { // arpeggiator, test: only the arpeggiator's bpm is in the reference tree, its behaviour is not
+          p.warnings.push_back("controller device '" + d.id + "' (" + d.kind + ") skipped: only tracks and trips drive this path");
+          continue;
+        }
+        p.controllers.push_back(c);
         continue;
       } else { // DeviceSettings has three variants (settings/src/lib.rs:42-46); projects/tests/invalid-project.json "should fail to load" on a fourth
         throw std::runtime_error("project: unknown device class '" + cls + "' (expected instrument, controller or effect)");
@@ -395,6 +416,30 @@ ProjectDesc parse_project(const std::string& text, const std::string& assets_roo
         }
       p.trips.push_back(t);
     }
+  // controls: {id, source, target: {id, param}} — a controller device's value onto one parameter of a device
+  if (const json5::Value* cv = root->get("controls"))
+    for (auto& x : cv->arr) {
+      if (!x->is_object()) continue;
+      ProjectDesc::Control c;
+      c.id = x->string_or("id", "");
+      c.source = x->string_or("source", "");
+      if (const json5::Value* tg = x->get("target")) { c.target = tg->string_or("id", ""); c.param = tg->string_or("param", ""); }
+      const ProjectDesc::ControllerDev* src = nullptr;
+      for (const auto& k : p.controllers) if (k.id == c.source) src = &k;
+      if (!src) { p.warnings.push_back("control " + c.id + " has no source: '" + c.source + "' is not a controller device of this project"); continue; }
+      const ProjectDesc::Device* dst = nullptr;
+      for (const auto& d : p.devices) if (d.id == c.target) dst = &d;
+      if (!dst) { p.warnings.push_back("control " + c.id + " controls nonexistent device " + c.target); continue; }
+      const int idx = dst->is_effect ? fx_control_index_for_name(c.param) : bank_control_index_for_name(c.param);
+      if (idx < 0) { p.warnings.push_back("control " + c.id + ": " + c.target + " has no parameter '" + c.param + "'"); continue; }
+      if (dst->is_effect && dst->fx_kind != GROOVE_FX_MIXER && fx_control_device_linkable(dst->fx_kind, idx)) c.route = ProjectDesc::CONTROL_ON_DEVICE;
+      else if (src->kind == "lfo") c.route = ProjectDesc::CONTROL_PER_BLOCK;
+      else { // the host derives that parameter's device form: a sample of a device block would have to come back to it in every block
+        p.warnings.push_back("control " + c.id + " dropped: a signal source onto '" + c.param + "' would need a download per block");
+        continue;
+      }
+      p.controls.push_back(c);
+    }
   return p;
 }
 
@@ -428,6 +473,18 @@ std::string describe(const ProjectDesc& p) {
     double beats = 0; for (auto& s : p.trips[i].steps) beats += s.beats;
     o << (i ? "," : "") << "{\"id\":\"" << p.trips[i].id << "\",\"target\":\"" << p.trips[i].target << "\",\"param\":\"" << p.trips[i].param
       << "\",\"steps\":" << p.trips[i].steps.size() << ",\"beats\":" << beats << ",\"first_kind\":" << (p.trips[i].steps.empty() ? -1 : (int)p.trips[i].steps[0].kind) << "}";
+  }
+  o << "],\"controllers\":[";
+  for (size_t i = 0; i < p.controllers.size(); ++i) {
+    const auto& c = p.controllers[i];
+    o << (i ? "," : "") << "{\"id\":\"" << c.id << "\",\"kind\":\"" << c.kind << "\",\"waveform\":" << c.waveform << ",\"duty\":" << c.duty
+      << ",\"frequency\":" << c.frequency << "}";
+  }
+  o << "],\"controls\":[";
+  for (size_t i = 0; i < p.controls.size(); ++i) {
+    const auto& c = p.controls[i];
+    o << (i ? "," : "") << "{\"id\":\"" << c.id << "\",\"source\":\"" << c.source << "\",\"target\":\"" << c.target << "\",\"param\":\"" << c.param
+      << "\",\"route\":\"" << (c.route == ProjectDesc::CONTROL_ON_DEVICE ? "device" : "per-block") << "\"}";
   }
   o << "],\"warnings\":" << p.warnings.size() << "}";
   return o.str();
@@ -602,6 +659,18 @@ int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets
     o.get((Uid)uid)->name = d.id;
     uid_of[d.id] = (Uid)uid;
     if (!d.is_effect && o.connect_midi_downstream((Uid)uid, (uint8_t)d.midi_in)) return 1;
+  }
+  for (const auto& c : p.controllers) { // after the devices, as handle_work meets them (controllers work in the order they were added)
+    Uid uid;
+    if (c.kind == "lfo") uid = o.add(std::unique_ptr<Entity>(new LfoController(c.waveform, c.duty, c.frequency)));
+    else uid = o.add(std::unique_ptr<Entity>(new SignalPassthrough()));
+    o.get(uid)->name = c.id;
+    uid_of[c.id] = uid;
+  }
+  for (const auto& c : p.controls) {
+    auto src = uid_of.find(c.source), dst = uid_of.find(c.target);
+    if (src == uid_of.end() || dst == uid_of.end()) continue; // (parse_project has warned)
+    if (o.link_control(src->second, dst->second, c.param) == 1) return 1;
   }
   for (const auto& cable : p.patch_cables)
     for (size_t i = 0; i + 1 < cable.size(); ++i) {

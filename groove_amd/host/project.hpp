@@ -5,6 +5,7 @@
 //   DeviceSettings / *Settings enums  settings/src/lib.rs:40-46, instruments.rs:26-39, effects.rs:19-56
 //   PatternSettings / TrackSettings   settings/src/lib.rs:48-88
 //   ControlPath / ControlTrip         settings/src/controllers.rs:18-99
+//   ControllerSettings, `controls`    settings/src/controllers.rs:103-112, songs.rs (ControlSettings{id, source, target})
 //   WelshPatchSettings                settings/src/patches.rs:20-47, 87-170, 204-314
 // Parsing is split from instantiation so that the schema handling can be tested without a GPU.
 #pragma once
@@ -29,6 +30,17 @@ struct ProjectDesc {
     uint32_t fx_kind = GROOVE_FX_MIXER;
     groove_fx_params fx{};
   };
+  // controller devices (settings/src/controllers.rs:103-112) and the `controls` links from one of them to a device's parameter
+  struct ControllerDev {
+    std::string id;
+    std::string kind;        // "lfo" or "signal-passthrough-controller"
+    int midi_in = 0, midi_out = 0;
+    uint32_t waveform = GROOVE_WAVE_SINE; // lfo
+    float duty = 0.5f;
+    double frequency = 1.0;  // lfo, Hz
+  };
+  enum ControlRoute { CONTROL_ON_DEVICE = 0, CONTROL_PER_BLOCK = 1 }; // a groove_ctl_link / Orchestrator::control_effect once per block
+  struct Control { std::string id, source, target, param; int route = CONTROL_ON_DEVICE; };
   struct Note { int channel, key; double start_beat, duration_beats; };
   struct Trip { std::string id, target, param; double start_beat = 0.0; std::vector<ControlStep> steps; };
 
@@ -41,6 +53,8 @@ struct ProjectDesc {
   std::vector<Note> notes;   // tracks x patterns flattened to absolute beats
   double end_beats = 0.0;    // the sequencer ends at the end of its last full measure
   std::vector<Trip> trips;
+  std::vector<ControllerDev> controllers;
+  std::vector<Control> controls; // the links that resolve (the others are warnings)
   std::vector<std::string> warnings; // the reference eprintln!s and continues (songs.rs:137, 152-156)
 };
 

@@ -30,6 +30,7 @@ def load():
         "gh_add_timer": (i, [vp, d]), "gh_add_sequencer": (i, [vp]),
         "gh_sequencer_insert": (i, [vp, i, i, i, d, d]), "gh_sequencer_set_end": (i, [vp, i, d]),
         "gh_add_control_trip": (i, [vp, i, C.c_char_p, d]), "gh_control_trip_add_step": (i, [vp, i, i, d, d, d]),
+        "gh_add_lfo_controller": (i, [vp, u32, d, d]), "gh_add_signal_passthrough": (i, [vp]), "gh_link_control": (i, [vp, i, i, C.c_char_p]),
         "gh_control_step_value": (d, [i, d, d, d]), "gh_last_allocated_voice": (i, [vp, i]),
         "gh_gather_audio": (i, [vp, u32, _fp]), "gh_performance_frames": (C.c_uint64, [vp]),
         "gh_run": (C.c_int64, [vp, u32, _fp, C.c_uint64, i]), "gh_render_to_wav": (i, [vp, u32, C.c_char_p]),
@@ -108,6 +109,27 @@ class Orchestrator:
 
     def control_trip_add_step(self, uid, kind, start, end, beats):
         self._chk(self.L.gh_control_trip_add_step(self.h, uid, kind, start, end, beats))
+
+    def add_lfo_controller(self, waveform, frequency_hz, duty=0.5):
+        """LfoController{waveform, frequency}: a controller device whose links are worked once per block."""
+        uid = self.L.gh_add_lfo_controller(self.h, waveform, duty, frequency_hz)
+        if uid < 0:
+            raise RuntimeError(self.L.gh_last_error(self.h).decode())
+        return uid
+
+    def add_signal_passthrough(self):
+        """SignalPassthroughController: patchable like an effect (identity, one lane); the source of a sidechain link."""
+        return self.L.gh_add_signal_passthrough(self.h)
+
+    def link_control(self, source, target, param):
+        """Orchestrator::link_control.  True: linked; False: dropped (a signal source onto a parameter only the host can derive —
+        last_error() says why); raises on an error."""
+        rc = self.L.gh_link_control(self.h, source, target, param.encode())
+        if rc == 1:
+            raise RuntimeError(self.L.gh_last_error(self.h).decode())
+        return rc == 0
+
+    def last_error(self): return self.L.gh_last_error(self.h).decode()
 
     def last_allocated_voice(self, uid): return self.L.gh_last_allocated_voice(self.h, uid)
 

@@ -89,6 +89,11 @@ SYMBOLS = {
     "groove_bank_render_chain_async": (_i, [_vp, _u32, _vp, _vp, _u32, C.POINTER(_u32)]),
     "groove_fx_set_param": (_i, [_vp, _u32, _u32, _d]),
     "groove_fx_set_params": (_i, [_vp, C.POINTER(T.FxParams), _u32]),
+    "groove_ctl_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),
+    "groove_ctl_link_capture": (_i, [_vp, _vp, _u32]),
+    "groove_ctl_link_apply": (_i, [_vp, C.c_uint64]),
+    "groove_ctl_link_reset": (_i, [_vp]),
+    "groove_ctl_link_destroy": (_i, [_vp]),
     "groove_mix": (_i, [_vp, _vpp, _u32, _u32, _vp, _i]),
     "groove_bus_create": (_i, [_vp, C.c_size_t, _vpp]),
     "groove_bus_destroy": (_i, [_vp, _vp]),

@@ -36,6 +36,7 @@ typedef struct groove_ctx groove_ctx;     /* one device + one stream            
 typedef struct groove_bank groove_bank;   /* an instrument: N homogeneous voices, one lane each */
 typedef struct groove_fx groove_fx;       /* an effect applied per lane to an N-lane block  */
 typedef struct groove_block groove_block; /* device stereo block [2][frames_cap][n] fp32    */
+typedef struct groove_ctl_link groove_ctl_link; /* a controller linked to one parameter of an effect */
 
 /* ---- context ------------------------------------------------------------------------ */
 /* Orchestrator::new_with + device selection (orchestrator.rs:522-568). */
@@ -296,6 +297,37 @@ int groove_bank_render_chain_async(groove_bank* bank, uint32_t frames, groove_bl
 int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, double value01);
 /* Replace all per-lane parameters (non-UNIFORM fields only may change). */
 int groove_fx_set_params(groove_fx* fx, const groove_fx_params* p, uint32_t n);
+
+/* ---- control links (IsController -> Controllable, resident on the device) ------------------ */
+/* A controller device (ControllerSettings::LfoController / SignalPassthroughController, settings/src/controllers.rs:103-112)
+ * linked to one parameter of an effect: the `controls` entry `source -> target.param` that Orchestrator::link_control
+ * records (orchestrator.rs:1279-1294).  The reference works every controller once per tick and dispatches the ControlValue it
+ * emits to the linked Controllable::control_set_param_by_index before gather_audio (orchestrator.rs:631-708, 856-877); here
+ * a small kernel on the ctx stream writes the value into the target's device parameters, with NO host wait and no copy
+ * (groove_fx_set_param re-uploads whole parameter arrays and waits for the ctx stream around each copy: fine for a change
+ * now and then, not for one in every block).  docs/DSP_SPEC.md section 13 defines the value and target laws.
+ *   src[n_src]: n_src equals the target's lane count, or is 1 and is broadcast to every lane; all of one `source` kind.
+ *   control_index: GROOVE_CTL_FX_CEILING (Gain), _BITS (Bitcrusher), _ATTENUATION (Reverb), _THRESHOLD (Compressor / Limiter)
+ *   — the parameters whose device form IS the value.  _CUTOFF, _Q, _PASSBAND_RIPPLE (coefficients derived on the host in f64)
+ *   and _WET (it chooses a kernel path on the host) are refused, as are noise / none waveforms (no closed form for the state
+ *   of a noise generator after n ticks).
+ * A link does not update the host's copy of the target's parameters: a later groove_fx_set_param / groove_fx_set_params on the
+ * target re-uploads that copy and so overwrites the linked parameter until the link's next apply. */
+int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                           groove_ctl_link** out);
+/* TransformsAudio::transform_audio of a SignalPassthroughController: the identity on `block` (it is only read), which keeps, per
+ * lane, clamp((L + R) / 2, -1, 1) of frame `frames - 1` for the next groove_ctl_link_apply.  Signal links only; the block has
+ * n_src lanes.  Ordered behind whatever fills the block, like every call that reads one. */
+int groove_ctl_link_capture(groove_ctl_link* link, groove_block* block, uint32_t frames);
+/* IsController::work for the block whose first frame is `at_frame` (frames since Orchestrator::skip_to_start), followed by the
+ * dispatch of its ControlValue: an LFO link evaluates its oscillator at at_frame; a signal link hands on what it captured last
+ * (nothing captured yet, or since a reset: the target is left untouched).  Ordered like groove_fx_set_param — behind every use of
+ * the target submitted so far, ahead of every later one.  An error once the target has been destroyed. */
+int groove_ctl_link_apply(groove_ctl_link* link, uint64_t at_frame);
+/* Resets::reset (Orchestrator::skip_to_start, orchestrator.rs:971-983): a signal link forgets what it captured. */
+int groove_ctl_link_reset(groove_ctl_link* link);
+/* Orchestrator::unlink_control (orchestrator.rs:1296-1320).  groove_shutdown frees the links that are still alive. */
+int groove_ctl_link_destroy(groove_ctl_link* link);
 
 /* ---- mix bus (Orchestrator::gather_audio, orchestrator.rs:367-470) ------------------------ */
 /* bus_dev[f][ch] (+)= sum over blocks and lanes of block[ch][f][lane]. */

@@ -189,6 +189,27 @@ typedef enum {
   GROOVE_CTL_WELSH_CUTOFF = 34       /* "filter-cutoff" (value01 → Hz) */
 } groove_control_index;
 
+/* Controller devices (the schema's third device class, settings/src/controllers.rs: "lfo", "signal-passthrough-controller")
+ * as the SOURCE of a control link, groove_ctl_link_create.  docs/DSP_SPEC.md section 13 defines the value laws. */
+typedef enum {
+  GROOVE_CTL_SRC_LFO = 0,   /* "lfo"{waveform, frequency}: an oscillator of DSP_SPEC section 2, read once per block     */
+  GROOVE_CTL_SRC_SIGNAL = 1 /* "signal-passthrough-controller": the last frame of the block it has passed on            */
+} groove_ctl_source_kind;
+/* How a captured sample m in [-1, 1] becomes a ControlValue in 0..1 (signal sources only). */
+typedef enum {
+  GROOVE_CTL_LAW_BIPOLAR = 0,           /* (m + 1) / 2: BipolarNormal -> Normal, the schema device's law              */
+  GROOVE_CTL_LAW_AMPLITUDE = 1,         /* |m|                                                                          */
+  GROOVE_CTL_LAW_AMPLITUDE_INVERTED = 2 /* 1 - |m|: the louder the source, the lower the target (a ducking sidechain)   */
+} groove_ctl_law;
+/* One source lane of a control link.  Unused fields are ignored (waveform, duty, frequency_hz by a signal source; law by an LFO). */
+typedef struct {
+  uint32_t source;     /* groove_ctl_source_kind; equal across the lanes of one link                                    */
+  uint32_t waveform;   /* groove_waveform: sine, triangle, square, sawtooth, pulse-width, triangle-sine                 */
+  float duty;          /* PulseWidth(f32) duty cycle; ignored otherwise                                                 */
+  double frequency_hz; /* LFO rate                                                                                      */
+  uint32_t law;        /* groove_ctl_law                                                                                */
+} groove_ctl_source;
+
 #ifdef __cplusplus
 }
 #endif
