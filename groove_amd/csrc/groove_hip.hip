@@ -242,7 +242,6 @@ struct groove_ctx {
   // which had nothing to do with events.  On again in round 4; GROOVE_BIND_EVENTS=0 for A/B.)
   bool bind_events = true;
   uint32_t fx_seg_max_lanes = 49152;     // biquad banks of up to this many lane-channels take the four-segment kernel (measured, tools/fx_bench.py: 8,192 lane-channels 17.5 -> 9.3 us, 32,768 19.4 -> 15.6, 131,072 42.9 -> 58.4; 0 = never)
-  uint32_t fx_tp_wide_min_lanes = 8192;  // from this many lane-channels the time-parallel IIR kernels take 32-wide tiles
   // groove_set_fx_allpass_stream: the side stream that carries the all-passes of chains that END in a reverb (-1: the ctx stream
   // carries them, behind the run).  deferred_ap: lane sums written on that stream that groove_mix_deferred has taken and the NEXT
   // all-pass launch (same stream: ordered) puts on their bus.
@@ -2421,24 +2420,75 @@ int groove_fx_reset(groove_fx* fx) {
   return 0;
 }
 // ---- effect stages ---------------------------------------------------------------------
-// Can this effect, for a block of `frames`, run as a stage of a fused run (kernels.h, fx_run_kernel)?  The element-wise
-// kinds always can; a delay line can when it is at least a block long (no feedback inside the block).
-static bool fx_run_capable(const groove_fx* fx, uint32_t frames) {
+// THE effect form decision: groove_fx_chain_process (which stages join a fused run), fx_launch_run (what follows a reverb's
+// combs), fx_launch_serial (which kernel walks the frames) and groove_fx_kernel_form all ask here.  kFxFormNames holds one
+// string per form, in the enum's order: the only list of them (groove_fx_kernel_form_name hands it out).
+enum class FxForm : uint32_t {
+  Identity, RunStage,
+  RunDirectAp, RunDirect, RunChunked, RunSeq,
+  BiquadTp, BiquadSeg, BiquadSerial, Lp24Tp, Lp24Serial,
+  Delay16, Delay1, Chorus16, Chorus1, Reverb8, Reverb1,
+  Count
+};
+static const char* const kFxFormNames[(size_t)FxForm::Count] = {
+  "identity (Mixer: no launch)",
+  "fx_run_kernel (a stage of the fused run)",
+  "fx_run_kernel + fx_reverb_allpass_direct_kernel (combs in the fused run, direct all-pass on the all-pass stream)",
+  "fx_run_kernel + fx_reverb_allpass_direct_kernel (combs in the fused run, direct all-pass behind it)",
+  "fx_run_kernel + fx_reverb_allpass_chunked_kernel (combs in the fused run, chunked all-pass)",
+  "fx_run_kernel + fx_reverb_allpass_kernel<32> (combs in the fused run, sequential all-pass)",
+  "fx_biquad_tp_kernel (IIR time-parallel)",
+  "fx_biquad_seg_kernel (IIR four-segment)",
+  "fx_biquad_kernel<16> (IIR serial)",
+  "fx_lp24_tp_kernel (IIR time-parallel)",
+  "fx_lp24_kernel<16> (IIR serial)",
+  "fx_delay_kernel<16> (delay serial, chunk 16)",
+  "fx_delay_kernel<1> (delay serial, chunk 1)",
+  "fx_chorus_kernel<16> (chorus serial, chunk 16)",
+  "fx_chorus_kernel<1> (chorus serial, chunk 1)",
+  "fx_reverb_kernel<8> (reverb serial, chunk 8)",
+  "fx_reverb_kernel<1> (reverb serial, chunk 1)",
+};
+// `last_on_ctx`: the launch is the last of its chain and goes to the ctx stream (only such a launch may leave for the all-pass
+// stream).  The element-wise kinds are always stages of a fused run (kernels.h, fx_run_kernel); a delay line is one when it is
+// at least a block long (no feedback inside the block).
+static FxForm fx_form_of(const groove_fx* fx, const groove_block* io, uint32_t frames, bool last_on_ctx) {
+  const groove_ctx* ctx = fx->ctx;
+  const size_t n = fx->n;
   switch (fx->kind) {
-    case GROOVE_FX_GAIN: case GROOVE_FX_BITCRUSHER: case GROOVE_FX_LIMITER: case GROOVE_FX_COMPRESSOR: return true;
-    case GROOVE_FX_DELAY: return fx->N >= frames;
+    case GROOVE_FX_MIXER: return FxForm::Identity;
+    case GROOVE_FX_GAIN: case GROOVE_FX_BITCRUSHER: case GROOVE_FX_LIMITER: case GROOVE_FX_COMPRESSOR: return FxForm::RunStage;
+    case GROOVE_FX_BIQUAD_LP12: case GROOVE_FX_BIQUAD_HP12: case GROOVE_FX_BIQUAD_BP12: case GROOVE_FX_BIQUAD_BS12:
+    case GROOVE_FX_BIQUAD_AP12: case GROOVE_FX_BIQUAD_PEAK12: case GROOVE_FX_BIQUAD_LSHELF12: case GROOVE_FX_BIQUAD_HSHELF12:
+      // few lane-channels: one wavefront each, frames over its lanes (fx_tp.h); many: one thread each, frames serial
+      if (frames <= kTpMaxFrames && 2 * n <= ctx->fx_tp_max_lanes && ctx->tp_max_voices) return FxForm::BiquadTp;
+      if (frames <= (uint32_t)(kBqSegs * kBqSegMax) && frames >= 16 && 2 * n <= ctx->fx_seg_max_lanes) return FxForm::BiquadSeg; // four time segments per lane-channel
+      return FxForm::BiquadSerial;
+    case GROOVE_FX_BIQUAD_LP24:
+      if (frames <= kTpMaxFrames && 4 * n <= ctx->fx_tp_max_lanes && ctx->tp_max_voices) return FxForm::Lp24Tp;
+      return FxForm::Lp24Serial;
+    case GROOVE_FX_DELAY:
+      if (fx->N >= frames) return FxForm::RunStage;
+      return fx->N >= 16 ? FxForm::Delay16 : FxForm::Delay1; // chunked loads need every read of a chunk to precede its writes: N >= chunk
     case GROOVE_FX_CHORUS: {
       const uint32_t nearest = fx->N - (fx->voices - 1) * fx->spacing; // newest tap: pushed this many frames ago
-      return nearest >= frames && (fx->voices == 1 || fx->spacing >= frames);
+      if (nearest >= frames && (fx->voices == 1 || fx->spacing >= frames)) return FxForm::RunStage;
+      return nearest >= 16 && (fx->voices == 1 || fx->spacing >= 16) ? FxForm::Chorus16 : FxForm::Chorus1;
     }
     case GROOVE_FX_REVERB: { // combs in the run, the two all-passes behind it
       uint32_t shortest_comb = fx->geo.N[0];
       for (int i = 1; i < 4; ++i) shortest_comb = std::min(shortest_comb, fx->geo.N[i]);
-      return fx->all_wet && shortest_comb >= frames && std::min(fx->geo.N[4], fx->geo.N[5]) >= 32;
+      const uint32_t shortest_ap = std::min(fx->geo.N[4], fx->geo.N[5]);
+      if (!(fx->all_wet && shortest_comb >= frames && shortest_ap >= 32)) return std::min(shortest_comb, shortest_ap) >= 8 ? FxForm::Reverb8 : FxForm::Reverb1;
+      // the direct all-pass form unrolls at most 8 hops per frame, and wants the comb sum in a staging block of the block's capacity
+      const bool direct = !ctx->seq_allpass && !ctx->chunked_allpass && frames <= 8 * shortest_ap && (size_t)2 * io->cap * n * 4 <= ((size_t)1 << 30);
+      if (direct) return last_on_ctx && ctx->fx_ap_stream >= 0 && io->ev_free ? FxForm::RunDirectAp : FxForm::RunDirect;
+      return ctx->seq_allpass ? FxForm::RunSeq : FxForm::RunChunked;
     }
-    default: return false;
+    default: return FxForm::Count; // (groove_fx_create refuses unknown kinds)
   }
 }
+static bool fx_form_is_run(FxForm f) { return f >= FxForm::RunStage && f <= FxForm::RunSeq; }
 static bool fx_is_iir(uint32_t kind) {
   switch (kind) {
     case GROOVE_FX_BIQUAD_LP12: case GROOVE_FX_BIQUAD_HP12: case GROOVE_FX_BIQUAD_BP12: case GROOVE_FX_BIQUAD_BS12:
@@ -2466,15 +2516,16 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
   a.src = io->d; a.src_chs = chs;
   a.dst = io->d; a.dst_chs = chs;
   groove_fx* rv = run[count - 1]->kind == GROOVE_FX_REVERB ? run[count - 1] : nullptr;
-  bool direct = false, on_ap = false;
+  bool direct = false, on_ap = false, seq = false;
   if (rv) {
     a.geo = rv->geo;
     // the direct all-pass form wants the comb sum in a staging block (it reads other frames than the one it writes)
-    const uint32_t shortest_ap = std::min(rv->geo.N[4], rv->geo.N[5]);
-    direct = !ctx->seq_allpass && !ctx->chunked_allpass && frames <= 8 * shortest_ap && (size_t)2 * io->cap * n * 4 <= ((size_t)1 << 30);
     // The all-pass stream: the chain's LAST launch (nothing on the ctx stream reads the block behind it; its lane sums go to the
     // bus through groove_mix / groove_mix_deferred) leaves the ctx stream, so the next block's run follows this one directly.
-    on_ap = direct && last && ctx->fx_ap_stream >= 0 && st == ctx->stream && io->ev_free;
+    const FxForm form = fx_form_of(rv, io, frames, last && st == ctx->stream);
+    on_ap = form == FxForm::RunDirectAp;
+    direct = on_ap || form == FxForm::RunDirect;
+    seq = form == FxForm::RunSeq;
     if (!on_ap && rv->ap_busy) { if (ap_join(ctx)) return 1; rv->ap_busy = false; }
     if (direct && on_ap) {
       if (io->stage_cap < io->cap) { // (first use of the block on this path: nothing of the block's is in flight on that stream yet)
@@ -2557,7 +2608,7 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
         else hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<1>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
       }
       for (int i = 0; i < 2; ++i) std::swap(rv->geo.base[4 + i], rv->ap_alt[i]);
-    } else if (ctx->seq_allpass) {
+    } else if (seq) {
       hipLaunchKernelGGL(fx_reverb_allpass_kernel<32>, dim3(blocks_for(2 * (size_t)n)), blk, 0, st, io->d, n, frames, chs, rv->d_ring, g);
     } else { // chunks of one line length, parallel inside (kernels.h)
       const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(64, 2 * n / 512));
@@ -2570,60 +2621,47 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
   return 0;
 }
 // The kinds with feedback inside a block: the IIR filters, and delay lines shorter than the block.
-static int fx_launch_serial(groove_fx* fx, groove_block* io, uint32_t frames, hipStream_t st) {
+static int fx_launch_serial(groove_fx* fx, FxForm form, groove_block* io, uint32_t frames, hipStream_t st) {
   groove_ctx* ctx = fx->ctx;
   const uint32_t n = fx->n;
   const size_t chs = (size_t)io->cap * n;
   const dim3 blk(kThreads), lanes_grid(blocks_for(2 * (size_t)n));
   // (64-frame chunks instead of 16 were measured for the serial IIR kernels: no change at any bank size — the walk is
   // bound by its dependent f64 chain, not by the chunk loads.)
-  switch (fx->kind) {
-    case GROOVE_FX_BIQUAD_LP12:
-    case GROOVE_FX_BIQUAD_HP12:
-    case GROOVE_FX_BIQUAD_BP12:
-    case GROOVE_FX_BIQUAD_BS12:
-    case GROOVE_FX_BIQUAD_AP12:
-    case GROOVE_FX_BIQUAD_PEAK12:
-    case GROOVE_FX_BIQUAD_LSHELF12:
-    case GROOVE_FX_BIQUAD_HSHELF12:
-      // few lane-channels: one wavefront each, frames over its lanes (fx_tp.h); many: one thread each, frames serial
-      if (frames <= kTpMaxFrames && 2 * (size_t)n <= ctx->fx_tp_max_lanes && ctx->tp_max_voices) {
-        if (2 * (size_t)n >= ctx->fx_tp_wide_min_lanes) hipLaunchKernelGGL(fx_biquad_tp_kernel<kFxTileWide>, dim3((n + kFxTileWide - 1) / kFxTileWide, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
-        else hipLaunchKernelGGL(fx_biquad_tp_kernel<kFxTile>, dim3((n + kFxTile - 1) / kFxTile, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
-      }
-      else if (frames <= (uint32_t)(kBqSegs * kBqSegMax) && frames >= 16 && 2 * (size_t)n <= ctx->fx_seg_max_lanes) // four time segments per lane-channel
-        hipLaunchKernelGGL(fx_biquad_seg_kernel, dim3((2 * n + 63) / 64), blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
-      else
-        hipLaunchKernelGGL(fx_biquad_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
+  switch (form) {
+    case FxForm::BiquadTp:
+      hipLaunchKernelGGL(fx_biquad_tp_kernel, dim3((n + kFxTile - 1) / kFxTile, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
       break;
-    case GROOVE_FX_BIQUAD_LP24:
-      if (frames <= kTpMaxFrames && 4 * (size_t)n <= ctx->fx_tp_max_lanes && ctx->tp_max_voices) {
-        if (2 * (size_t)n >= ctx->fx_tp_wide_min_lanes) hipLaunchKernelGGL(fx_lp24_tp_kernel<kFxTileWide>, dim3((n + kFxTileWide - 1) / kFxTileWide, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
-        else hipLaunchKernelGGL(fx_lp24_tp_kernel<kFxTile>, dim3((n + kFxTile - 1) / kFxTile, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
-      }
-      else
-        hipLaunchKernelGGL(fx_lp24_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
+    case FxForm::BiquadSeg:
+      hipLaunchKernelGGL(fx_biquad_seg_kernel, dim3((2 * n + 63) / 64), blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
       break;
-    case GROOVE_FX_DELAY:
-      if (fx->N >= 16) // chunked loads need every read of a chunk to precede its writes: N >= chunk
-        hipLaunchKernelGGL(fx_delay_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->d_wet);
-      else hipLaunchKernelGGL(fx_delay_kernel<1>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->d_wet);
+    case FxForm::BiquadSerial:
+      hipLaunchKernelGGL(fx_biquad_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
       break;
-    case GROOVE_FX_CHORUS: {
-      const uint32_t nearest = fx->N - (fx->voices - 1) * fx->spacing;
-      if (nearest >= 16 && (fx->voices == 1 || fx->spacing >= 16))
-        hipLaunchKernelGGL(fx_chorus_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->voices, fx->spacing, fx->d_wet);
-      else hipLaunchKernelGGL(fx_chorus_kernel<1>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->voices, fx->spacing, fx->d_wet);
+    case FxForm::Lp24Tp:
+      hipLaunchKernelGGL(fx_lp24_tp_kernel, dim3((n + kFxTile - 1) / kFxTile, 2), dim3(kFxTpThreads), 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
       break;
-    }
-    case GROOVE_FX_REVERB: {
+    case FxForm::Lp24Serial:
+      hipLaunchKernelGGL(fx_lp24_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_coef, fx->d_st, fx->d_wet);
+      break;
+    case FxForm::Delay16:
+      hipLaunchKernelGGL(fx_delay_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->d_wet);
+      break;
+    case FxForm::Delay1:
+      hipLaunchKernelGGL(fx_delay_kernel<1>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->d_wet);
+      break;
+    case FxForm::Chorus16:
+      hipLaunchKernelGGL(fx_chorus_kernel<16>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->voices, fx->spacing, fx->d_wet);
+      break;
+    case FxForm::Chorus1:
+      hipLaunchKernelGGL(fx_chorus_kernel<1>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->N, fx->w, fx->voices, fx->spacing, fx->d_wet);
+      break;
+    case FxForm::Reverb8:
+    case FxForm::Reverb1:
       if (fx_ap_settle(fx)) return 1;
-      uint32_t shortest = fx->geo.N[0];
-      for (int i = 1; i < 6; ++i) shortest = std::min(shortest, fx->geo.N[i]);
-      if (shortest >= 8) hipLaunchKernelGGL(fx_reverb_kernel<8>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->geo, fx->d_fa, fx->d_wet);
+      if (form == FxForm::Reverb8) hipLaunchKernelGGL(fx_reverb_kernel<8>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->geo, fx->d_fa, fx->d_wet);
       else hipLaunchKernelGGL(fx_reverb_kernel<1>, lanes_grid, blk, 0, st, io->d, n, frames, chs, fx->d_ring, fx->geo, fx->d_fa, fx->d_wet);
       break;
-    }
     default: return fail(ctx, "groove_fx_process: unknown kind");
   }
   fx_advance(fx, frames);
@@ -2664,12 +2702,13 @@ int groove_fx_chain_process(groove_fx* const* chain, uint32_t n_fx, groove_block
     if (fx->kind == GROOVE_FX_MIXER) continue; // identity
     if (fx_acquire_ctx(fx)) return 1;
     io->sums_valid = false; // the block is transformed in place
-    if (fx_run_capable(fx, frames)) {
+    const FxForm form = fx_form_of(fx, io, frames, i == last_stage);
+    if (fx_form_is_run(form)) {
       run[count++] = fx;
       if (count == kRunMaxStages || fx->kind == GROOVE_FX_REVERB) { if (flush(i == last_stage)) return 1; }
     } else {
       if (flush(false)) return 1;
-      if (fx_launch_serial(fx, io, frames, ctx->stream)) return 1;
+      if (fx_launch_serial(fx, form, io, frames, ctx->stream)) return 1;
     }
   }
   return flush(true);
@@ -2710,7 +2749,7 @@ int groove_fx_chain_process_async(groove_fx* const* chain, uint32_t n_fx, groove
       GHIP(ctx, hipStreamWaitEvent(st, fx->ev_done, 0));
     }
     io->sums_valid = false;
-    if (fx_launch_serial(fx, io, frames, st)) return 1;
+    if (fx_launch_serial(fx, fx_form_of(fx, io, frames, false), io, frames, st)) return 1;
     GHIP(ctx, hipEventRecord(fx->ev_done, st));
     fx->done_recorded = true;
     fx->last_side = k;
@@ -2743,6 +2782,12 @@ int groove_bank_render_chain_async(groove_bank* b, uint32_t frames, groove_block
   *n_done = taken + more;
   return 0;
 }
+const char* groove_fx_kernel_form(groove_fx* fx, groove_block* block, uint32_t frames) {
+  if (!fx || !block) return "";
+  const FxForm form = fx_form_of(fx, block, frames, true);
+  return form < FxForm::Count ? kFxFormNames[(size_t)form] : "";
+}
+const char* groove_fx_kernel_form_name(uint32_t index) { return index < (uint32_t)FxForm::Count ? kFxFormNames[index] : nullptr; }
 int groove_fx_process(groove_fx* fx, groove_block* io, uint32_t frames) {
   if (!fx || !io) return fail(nullptr, "groove_fx_process: NULL argument");
   return groove_fx_chain_process(&fx, 1, io, frames);

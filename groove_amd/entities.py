@@ -411,6 +411,11 @@ class Effect:
     def set_params(self, params):
         _lib.check(self.ctx.L.groove_fx_set_params(self.h, params, len(params)), self.ctx.h)
 
+    def kernel_form(self, block, frames=None):
+        """groove_fx_kernel_form: the kernel form transform_audio(block, frames) takes right now."""
+        frames = block.cap if frames is None else frames
+        return self.ctx.L.groove_fx_kernel_form(self.h, block.h, frames).decode()
+
     def reset(self):
         _lib.check(self.ctx.L.groove_fx_reset(self.h), self.ctx.h)
 

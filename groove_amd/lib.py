@@ -87,6 +87,8 @@ SYMBOLS = {
     "groove_fx_chain_process": (_i, [_vp, _u32, _vp, _u32]),
     "groove_fx_chain_process_async": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "groove_bank_render_chain_async": (_i, [_vp, _u32, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "groove_fx_kernel_form": (C.c_char_p, [_vp, _vp, _u32]),
+    "groove_fx_kernel_form_name": (C.c_char_p, [_u32]),
     "groove_fx_set_param": (_i, [_vp, _u32, _u32, _d]),
     "groove_fx_set_params": (_i, [_vp, C.POINTER(T.FxParams), _u32]),
     "groove_ctl_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),

@@ -293,6 +293,13 @@ int groove_fx_chain_process_async(groove_fx* const* chain, uint32_t n_fx, groove
  * written a second time).  Same results as the two calls to f64 rounding of the filter's start states.  *n_done as above. */
 int groove_bank_render_chain_async(groove_bank* bank, uint32_t frames, groove_block* out, groove_fx* const* chain, uint32_t n_fx,
                                    uint32_t* n_done);
+/* Which kernel form groove_fx_process(fx, block, frames) takes right now (a static string; diagnosis and tests).  The form
+ * follows from the effect's kind, its lane count, the block length and its line lengths; a reverb's direct all-pass form also
+ * depends on the block's capacity (its staging block), hence the block.  The answer is the one for an effect that is the LAST
+ * launch of its chain: a reverb further up a chain never rides the all-pass stream.  groove_fx_kernel_form_name(i) lists every
+ * string the query can return, i = 0, 1, ... until it returns NULL (the one list of them: the library's table, in enum order). */
+const char* groove_fx_kernel_form(groove_fx* fx, groove_block* block, uint32_t frames);
+const char* groove_fx_kernel_form_name(uint32_t index);
 /* Controllable for effects; lane = GROOVE_ALL_VOICES for all lanes. */
 int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, double value01);
 /* Replace all per-lane parameters (non-UNIFORM fields only may change). */
