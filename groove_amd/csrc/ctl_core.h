@@ -6,6 +6,7 @@
 // compile this text with g++ and hold it against closed forms.
 #pragma once
 #include "dsp_core.h"
+#include "fx_coef.h"
 
 namespace groove {
 
@@ -51,12 +52,34 @@ GROOVE_HD float ctl_signal_value01(uint32_t law, float m) {
 
 // ------------------------------------------------------------------ targets
 // groove_fx_set_param's laws where the device form IS the value.  The others are derived on the host in f64 (cutoff, q,
-// passband-ripple -> coefficients) or choose a kernel path there (wet-dry-mix -> all_wet): a link cannot reach them.
+// passband-ripple -> coefficients; a FILTER link derives them on the device instead, below) or choose a kernel path there
+// (wet-dry-mix -> all_wet): a plain link cannot reach them.
 GROOVE_HD bool ctl_target_linkable(uint32_t control_index) {
   switch (control_index) {
     case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_BITS: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD: return true;
     default: return false;
   }
+}
+// The parameters a FILTER link (groove_ctl_filter_link_create) reaches: the link's kernel turns the value into the parameter by
+// groove_fx_set_param's law and derives the lane's coefficients on the device (fx_coef.h).  cutoff: every IIR kind; q: the kinds whose
+// formula reads it; passband-ripple: the 24 dB low-pass.
+GROOVE_HD bool ctl_target_derived(uint32_t kind, uint32_t control_index) {
+  switch (control_index) {
+    case GROOVE_CTL_FX_CUTOFF: return fx_kind_is_filter(kind);
+    case GROOVE_CTL_FX_Q: return kind == GROOVE_FX_BIQUAD_LP12 || kind == GROOVE_FX_BIQUAD_HP12 || kind == GROOVE_FX_BIQUAD_AP12;
+    case GROOVE_CTL_FX_PASSBAND_RIPPLE: return kind == GROOVE_FX_BIQUAD_LP24;
+    default: return false;
+  }
+}
+// A filter lane's parameter shadow on the device, [word][lane]: what deriving its coefficients reads (groove_fx: d_shadow).
+enum : uint32_t { CTL_SHADOW_CUTOFF = 0, CTL_SHADOW_Q = 1, CTL_SHADOW_RIPPLE = 2, CTL_SHADOW_BANDWIDTH = 3, CTL_SHADOW_DB_GAIN = 4, CTL_SHADOW_WORDS = 5 };
+GROOVE_HD uint32_t ctl_shadow_word(uint32_t control_index) {
+  return control_index == GROOVE_CTL_FX_CUTOFF ? CTL_SHADOW_CUTOFF : (control_index == GROOVE_CTL_FX_Q ? CTL_SHADOW_Q : CTL_SHADOW_RIPPLE);
+}
+// value01 (clamped like groove_fx_set_param's) -> the float groove_fx_params would hold
+GROOVE_HD float ctl_derived_param(uint32_t control_index, float value01) {
+  const double v = clamp01d((double)value01);
+  return control_index == GROOVE_CTL_FX_CUTOFF ? (float)fx_percent_to_frequency(v) : (float)fx_q_law(v);
 }
 GROOVE_HD bool ctl_target_is_uint(uint32_t control_index) { return control_index == GROOVE_CTL_FX_BITS; }
 GROOVE_HD float ctl_target_float(float value01) { return value01; } // ceiling, threshold, attenuation

@@ -1,4 +1,4 @@
-// ctl_link.h — the two kernels of a device-resident CONTROL LINK (include/groove_hip.h, groove_ctl_link_*).
+// ctl_link.h — the kernels of a device-resident CONTROL LINK (include/groove_hip.h, groove_ctl_link_*).
 //
 // A controller's value reaches its target effect without the host: the capture kernel keeps the last frame of the block a
 // signal passthrough has passed on, the apply kernel computes the control value (ctl_core.h) and writes it into the
@@ -46,6 +46,44 @@ __global__ __launch_bounds__(kThreads) void ctl_apply_kernel(uint32_t source, Ct
   }
   if (dst_u) dst_u[e] = ctl_target_bits(v);
   else dst_f[e] = ctl_target_float(v);
+}
+
+// A link onto a filter's cutoff, q or passband-ripple (ctl_target_derived): the control value becomes the parameter by
+// groove_fx_set_param's law, lands in the lane's word of the parameter shadow, and the lane's coefficients are derived from the five
+// shadow words in f64 (fx_coef.h: the host's own text) and stored where the IIR kernels read them, coef[k * n + lane].  A second link
+// onto the same effect runs behind this one on the ctx stream and loads what this one stored.
+__global__ __launch_bounds__(kThreads) void ctl_filter_apply_kernel(uint32_t source, CtlLanes src, uint32_t n_src, uint64_t at_frame,
+                                                                    const float* __restrict__ value, const uint32_t* __restrict__ captured,
+                                                                    uint32_t kind, uint32_t control_index, double sr,
+                                                                    float* __restrict__ shadow, double* __restrict__ coef, uint32_t n) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= n) return;
+  const uint32_t s = n_src == 1u ? 0u : e;
+  float v;
+  if (source == GROOVE_CTL_SRC_LFO) {
+    v = ctl_lfo_value01(src.waveform[s], src.delta64[s], src.duty64[s], at_frame);
+  } else {
+    if (*captured == 0u) return;
+    v = ctl_signal_value01(src.law[s], value[s]);
+  }
+  const uint32_t word = ctl_shadow_word(control_index);
+  const float mine = ctl_derived_param(control_index, v);
+  shadow[(size_t)word * n + e] = mine;
+  float p[CTL_SHADOW_WORDS];
+#pragma unroll
+  for (uint32_t k = 0; k < CTL_SHADOW_WORDS; ++k) p[k] = k == word ? mine : shadow[(size_t)k * n + e];
+  double c[6];
+  uint32_t nc = 5;
+  if (kind == GROOVE_FX_BIQUAD_LP24) {
+    fx_lp24_coeffs((double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_RIPPLE], sr, c);
+    nc = 6;
+  } else if (!fx_rbj_for_kind(kind, (double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_Q], (double)p[CTL_SHADOW_BANDWIDTH],
+                              (double)p[CTL_SHADOW_DB_GAIN], sr, c)) {
+    return; // (not an IIR kind: groove_ctl_filter_link_create refuses it)
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 6; ++k)
+    if (k < nc) coef[(size_t)k * n + e] = c[k];
 }
 
 } // namespace groove

@@ -5,6 +5,7 @@
 // Host only; shared by the C ABI implementation and the tests/emul numerics harness.
 #pragma once
 #include "dsp_core.h"
+#include "fx_coef.h"
 
 namespace groove {
 
@@ -222,80 +223,18 @@ GROOVE_HD void sampler_note(const SamplerParams& p, SamplerState& s, uint32_t ke
   }
 }
 
-// f64 coefficient sets for the effect kernels (host; identical to the oracle's math).
-inline void rbj_lowpass_h(double f0, double q, double fs, double* c5) {
-  const double w0 = 2.0 * 3.14159265358979323846 * f0 / fs, cw = cos(w0), sw = sin(w0);
-  const double alpha = sw / (2.0 * q), a0 = 1.0 + alpha;
-  c5[0] = (1.0 - cw) / 2.0 / a0; c5[1] = (1.0 - cw) / a0; c5[2] = (1.0 - cw) / 2.0 / a0;
-  c5[3] = -2.0 * cw / a0; c5[4] = (1.0 - alpha) / a0;
-}
-inline void rbj_highpass_h(double f0, double q, double fs, double* c5) {
-  const double w0 = 2.0 * 3.14159265358979323846 * f0 / fs, cw = cos(w0), sw = sin(w0);
-  const double alpha = sw / (2.0 * q), a0 = 1.0 + alpha;
-  c5[0] = (1.0 + cw) / 2.0 / a0; c5[1] = -(1.0 + cw) / a0; c5[2] = (1.0 + cw) / 2.0 / a0;
-  c5[3] = -2.0 * cw / a0; c5[4] = (1.0 - alpha) / a0;
-}
-// The remaining cookbook modes (doc/Audio-EQ-Cookbook.txt:113-198); parameter conventions: DSP_SPEC §4.
-inline double bw_octaves_h(double f0, double bw_hz) {
-  const double lo = f0 - 0.5 * bw_hz, hi = f0 + 0.5 * bw_hz;
-  if (!(lo > 0.0) || hi / lo > 256.0) return 8.0;
-  return log2(hi / lo);
-}
-inline void rbj_norm_h(double b0, double b1, double b2, double a0, double a1, double a2, double* c5) {
-  c5[0] = b0 / a0; c5[1] = b1 / a0; c5[2] = b2 / a0; c5[3] = a1 / a0; c5[4] = a2 / a0;
-}
+// f64 coefficient sets for the effect kernels (identical to the oracle's math).  The formulas are fx_coef.h's, one text for the
+// host and for the device's filter links; these are the host's names for them.
+inline void rbj_lowpass_h(double f0, double q, double fs, double* c5) { fx_rbj_lowpass(f0, q, fs, c5); }
+inline void rbj_highpass_h(double f0, double q, double fs, double* c5) { fx_rbj_highpass(f0, q, fs, c5); }
+inline double bw_octaves_h(double f0, double bw_hz) { return fx_bw_octaves(f0, bw_hz); }
+inline void rbj_norm_h(double b0, double b1, double b2, double a0, double a1, double a2, double* c5) { fx_rbj_norm(b0, b1, b2, a0, a1, a2, c5); }
 // Coefficients of any BiQuad 12 dB effect kind; false when `kind` is not one.
 inline bool rbj_for_kind_h(uint32_t kind, const groove_fx_params& p, double fs, double* c5) {
-  const double pi = 3.14159265358979323846;
-  const double f0 = p.cutoff_hz, w0 = 2.0 * pi * f0 / fs, cw = cos(w0), sw = sin(w0);
-  switch (kind) {
-    case GROOVE_FX_BIQUAD_LP12: rbj_lowpass_h(f0, p.q, fs, c5); return true;
-    case GROOVE_FX_BIQUAD_HP12: rbj_highpass_h(f0, p.q, fs, c5); return true;
-    case GROOVE_FX_BIQUAD_BP12: {
-      const double al = sw * sinh(log(2.0) / 2.0 * bw_octaves_h(f0, p.bandwidth_hz) * w0 / sw);
-      rbj_norm_h(al, 0.0, -al, 1.0 + al, -2.0 * cw, 1.0 - al, c5); return true;
-    }
-    case GROOVE_FX_BIQUAD_BS12: {
-      const double al = sw * sinh(log(2.0) / 2.0 * bw_octaves_h(f0, p.bandwidth_hz) * w0 / sw);
-      rbj_norm_h(1.0, -2.0 * cw, 1.0, 1.0 + al, -2.0 * cw, 1.0 - al, c5); return true;
-    }
-    case GROOVE_FX_BIQUAD_AP12: {
-      const double al = sw / (2.0 * p.q);
-      rbj_norm_h(1.0 - al, -2.0 * cw, 1.0 + al, 1.0 + al, -2.0 * cw, 1.0 - al, c5); return true;
-    }
-    case GROOVE_FX_BIQUAD_PEAK12: {
-      const double A = pow(10.0, p.db_gain / 40.0), al = sw / (2.0 * 0.70710678118654752440);
-      rbj_norm_h(1.0 + al * A, -2.0 * cw, 1.0 - al * A, 1.0 + al / A, -2.0 * cw, 1.0 - al / A, c5); return true;
-    }
-    case GROOVE_FX_BIQUAD_LSHELF12: {
-      const double A = pow(10.0, p.db_gain / 40.0), t = 2.0 * sqrt(A) * (sw / 2.0 * sqrt(2.0));
-      rbj_norm_h(A * ((A + 1) - (A - 1) * cw + t), 2 * A * ((A - 1) - (A + 1) * cw), A * ((A + 1) - (A - 1) * cw - t),
-                 (A + 1) + (A - 1) * cw + t, -2 * ((A - 1) + (A + 1) * cw), (A + 1) + (A - 1) * cw - t, c5);
-      return true;
-    }
-    case GROOVE_FX_BIQUAD_HSHELF12: {
-      const double A = pow(10.0, p.db_gain / 40.0), t = 2.0 * sqrt(A) * (sw / 2.0 * sqrt(2.0));
-      rbj_norm_h(A * ((A + 1) + (A - 1) * cw + t), -2 * A * ((A - 1) + (A + 1) * cw), A * ((A + 1) + (A - 1) * cw - t),
-                 (A + 1) - (A - 1) * cw + t, 2 * ((A - 1) - (A + 1) * cw), (A + 1) - (A - 1) * cw - t, c5);
-      return true;
-    }
-    default: return false;
-  }
+  return fx_rbj_for_kind(kind, p.cutoff_hz, p.q, p.bandwidth_hz, p.db_gain, fs, c5);
 }
 // out6 = b0,a1,a2 (section 1), b0,a1,a2 (section 2); y = b0 x + 2 b0 x1 + b0 x2 + a1 y1 + a2 y2
-inline void lp24_coeffs_h(double fc, double ripple, double fs, double* out6) {
-  if (fc > 0.49 * fs) fc = 0.49 * fs;
-  if (fc < 1.0) fc = 1.0;
-  const double k = tan(3.14159265358979323846 * fc / fs);
-  double sg = sinh(ripple), cg = cosh(ripple);
-  cg *= cg;
-  const double c0 = 1.0 / (cg - 0.85355339059327376220), c1 = k * c0 * sg * 1.84775906502257351226;
-  const double c2 = 1.0 / (cg - 0.14644660940672623780), c3 = k * c2 * sg * 0.76536686473017954346;
-  const double K = k * k;
-  const double a0 = 1.0 / (c1 + K + c0), a3 = 1.0 / (c3 + K + c2);
-  out6[0] = a0 * K; out6[1] = 2.0 * (c0 - K) * a0; out6[2] = (c1 - K - c0) * a0;
-  out6[3] = a3 * K; out6[4] = 2.0 * (c2 - K) * a3; out6[5] = (c3 - K - c2) * a3;
-}
+inline void lp24_coeffs_h(double fc, double ripple, double fs, double* out6) { fx_lp24_coeffs(fc, ripple, fs, out6); }
 inline uint32_t delay_frames_h(double seconds, double sr) {
   const double n = floor(seconds * sr + 0.5);
   if (!(n >= 1.0)) return 1u;                    // zero, negative, NaN
@@ -307,6 +246,6 @@ inline double decay_gain_h(double delay_s, double decay_s) {
 static const double kCombDelaysH[4] = {0.0297, 0.0371, 0.0411, 0.0437};
 static const double kAllpassDelaysH[2] = {0.005, 0.0017};
 static const double kAllpassDecaysH[2] = {0.09683, 0.03292};
-inline double percent_to_frequency_h(double p) { return 25.0 * pow(800.0, p); }
+inline double percent_to_frequency_h(double p) { return fx_percent_to_frequency(p); }
 
 } // namespace groove

@@ -158,6 +158,7 @@ struct groove_fx {
   uint32_t* d_ua = nullptr; // per-lane uint param (bits)
   float* d_wet = nullptr;
   double* d_coef = nullptr; // [5|6][n]
+  float* d_shadow = nullptr; // [CTL_SHADOW_WORDS][n]: the filter parameters the coefficients derive from; only once a filter link has been made onto the effect
   double* d_st = nullptr;   // [4][2n]
   float* d_ring = nullptr;  // rows of 2n floats
   size_t ring_rows = 0;
@@ -183,6 +184,7 @@ struct groove_ctl_link {
   groove_ctx* ctx;
   uint32_t source, n_src, control_index;
   groove_fx* target; // nullptr once the target has been destroyed (groove_fx_destroy clears it)
+  bool derived = false; // a filter link (groove_ctl_filter_link_create): the apply derives the target lanes' coefficients
   std::vector<groove_ctl_source> src;
   uint64_t* d_lanes = nullptr; // delta64[n_src], duty64[n_src], then waveform[n_src], law[n_src] as uint32
   float* d_value = nullptr;    // [n_src] captured samples (signal source)
@@ -1010,6 +1012,22 @@ int mix_one(groove_ctx* ctx, const groove_block* b, uint32_t frames, float* bus,
 }
 
 // ---- effects -------------------------------------------------------------------------
+// The device's copy of the filter parameters of every lane, for the filter links' kernel (ctl_link.h) to derive coefficients from.
+int fx_upload_shadow(groove_fx* fx) {
+  groove_ctx* ctx = fx->ctx;
+  const uint32_t n = fx->n;
+  std::vector<float> w((size_t)CTL_SHADOW_WORDS * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const groove_fx_params& p = fx->p[i];
+    w[(size_t)CTL_SHADOW_CUTOFF * n + i] = p.cutoff_hz;
+    w[(size_t)CTL_SHADOW_Q * n + i] = p.q;
+    w[(size_t)CTL_SHADOW_RIPPLE * n + i] = p.passband_ripple;
+    w[(size_t)CTL_SHADOW_BANDWIDTH * n + i] = p.bandwidth_hz;
+    w[(size_t)CTL_SHADOW_DB_GAIN * n + i] = p.db_gain;
+  }
+  GHIP(ctx, ctx_memcpy(ctx, fx->d_shadow, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
 int fx_upload_params(groove_fx* fx) {
   groove_ctx* ctx = fx->ctx;
   const uint32_t n = fx->n;
@@ -1052,6 +1070,7 @@ int fx_upload_params(groove_fx* fx) {
     }
     GHIP(ctx, ctx_memcpy(ctx, fx->d_coef, c.data(), c.size() * 8, hipMemcpyHostToDevice));
   }
+  if (fx->d_shadow) return fx_upload_shadow(fx); // a filter link's value is gone with its coefficients, until its next apply
   return 0;
 }
 
@@ -2403,7 +2422,7 @@ int groove_fx_destroy(groove_fx* fx) {
   for (groove_ctl_link* l : ctx->links) // a link onto this effect has no target any more: its next apply is an error, not a write
     if (l->target == fx) l->target = nullptr;
   (void)hipFree(fx->d_fa); (void)hipFree(fx->d_fb); (void)hipFree(fx->d_ua); (void)hipFree(fx->d_wet);
-  (void)hipFree(fx->d_coef); (void)hipFree(fx->d_st); (void)hipFree(fx->d_ring); (void)hipFree(fx->d_tmp);
+  (void)hipFree(fx->d_coef); (void)hipFree(fx->d_shadow); (void)hipFree(fx->d_st); (void)hipFree(fx->d_ring); (void)hipFree(fx->d_tmp);
   delete fx;
   return 0;
 }
@@ -2835,11 +2854,54 @@ int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, do
 }
 
 // ============================================================================ control links
+// What both kinds of link ask of their arguments and sources, and the link itself once the target has been accepted.
+static int ctl_link_check(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
+  const std::string w = std::string(who) + ": ";
+  if (!ctx || !src || !target || !out) return fail(ctx, w + "NULL argument");
+  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, w + "the target is not a live effect of this context");
+  if (n_src != 1 && n_src != target->n) return fail(ctx, w + "n_src must be the target's lane count, or 1 (broadcast)");
+  return 0;
+}
+static int ctl_link_check_sources(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src) {
+  const std::string w = std::string(who) + ": ";
+  for (uint32_t i = 0; i < n_src; ++i) {
+    if (src[i].source != GROOVE_CTL_SRC_LFO && src[i].source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, w + "unknown source kind");
+    if (src[i].source != src[0].source) return fail(ctx, w + "the lanes of one link share one source kind");
+    if (src[i].source == GROOVE_CTL_SRC_LFO) {
+      if (!ctl_lfo_waveform_ok(src[i].waveform))
+        return fail(ctx, w + "an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine (a noise generator's state at a block start has no closed form)");
+      if (!(src[i].frequency_hz >= 0.0) || !(src[i].frequency_hz < (double)ctx->sr)) return fail(ctx, w + "LFO frequency outside [0, sample rate)");
+    } else if (!ctl_signal_law_ok(src[i].law)) {
+      return fail(ctx, w + "unknown signal law");
+    }
+  }
+  return 0;
+}
+static int ctl_link_make(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                         bool derived, groove_ctl_link** out) {
+  const std::string w = std::string(who) + ": ";
+  GHIP(ctx, hipSetDevice(ctx->device));
+  groove_ctl_link* l = new groove_ctl_link();
+  l->ctx = ctx; l->source = src[0].source; l->n_src = n_src; l->control_index = control_index; l->target = target; l->derived = derived;
+  l->src.assign(src, src + n_src);
+  if (hipMalloc(&l->d_lanes, (size_t)3 * n_src * 8) != hipSuccess || hipMalloc(&l->d_value, (size_t)n_src * 4) != hipSuccess ||
+      hipMalloc(&l->d_captured, 4) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, w + "hipMalloc failed");
+  }
+  if (hipMemsetAsync(l->d_value, 0, (size_t)n_src * 4, ctx->stream) != hipSuccess || hipMemsetAsync(l->d_captured, 0, 4, ctx->stream) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, w + "hipMemsetAsync failed");
+  }
+  if (ctl_upload_lanes(l)) { groove_ctl_link_destroy(l); return 1; } // (its message stands)
+  ctx->links.push_back(l);
+  *out = l;
+  return 0;
+}
 int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
                            groove_ctl_link** out) {
-  if (!ctx || !src || !target || !out) return fail(ctx, "groove_ctl_link_create: NULL argument");
-  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_create: the target is not a live effect of this context");
-  if (n_src != 1 && n_src != target->n) return fail(ctx, "groove_ctl_link_create: n_src must be the target's lane count, or 1 (broadcast)");
+  const char* who = "groove_ctl_link_create";
+  if (ctl_link_check(ctx, who, src, n_src, target, out)) return 1;
   switch (control_index) {
     case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE:
       return fail(ctx, "groove_ctl_link_create: cutoff, q and passband-ripple become filter coefficients on the host (f64): not linkable on the device; use groove_fx_set_param");
@@ -2854,34 +2916,34 @@ int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32
                     (control_index == GROOVE_CTL_FX_ATTENUATION && target->kind == GROOVE_FX_REVERB) ||
                     (control_index == GROOVE_CTL_FX_THRESHOLD && (target->kind == GROOVE_FX_COMPRESSOR || target->kind == GROOVE_FX_LIMITER));
   if (!fits) return fail(ctx, "groove_ctl_link_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
-  for (uint32_t i = 0; i < n_src; ++i) {
-    if (src[i].source != GROOVE_CTL_SRC_LFO && src[i].source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_create: unknown source kind");
-    if (src[i].source != src[0].source) return fail(ctx, "groove_ctl_link_create: the lanes of one link share one source kind");
-    if (src[i].source == GROOVE_CTL_SRC_LFO) {
-      if (!ctl_lfo_waveform_ok(src[i].waveform))
-        return fail(ctx, "groove_ctl_link_create: an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine (a noise generator's state at a block start has no closed form)");
-      if (!(src[i].frequency_hz >= 0.0) || !(src[i].frequency_hz < (double)ctx->sr)) return fail(ctx, "groove_ctl_link_create: LFO frequency outside [0, sample rate)");
-    } else if (!ctl_signal_law_ok(src[i].law)) {
-      return fail(ctx, "groove_ctl_link_create: unknown signal law");
-    }
+  if (ctl_link_check_sources(ctx, who, src, n_src)) return 1;
+  return ctl_link_make(ctx, who, src, n_src, target, control_index, false, out);
+}
+int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                                  groove_ctl_link** out) {
+  const char* who = "groove_ctl_filter_link_create";
+  if (ctl_link_check(ctx, who, src, n_src, target, out)) return 1;
+  switch (control_index) {
+    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE: break;
+    case GROOVE_CTL_FX_WET:
+      return fail(ctx, "groove_ctl_filter_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+    case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_BITS: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD:
+      return fail(ctx, "groove_ctl_filter_link_create: a filter link reaches cutoff, q or passband-ripple; this parameter's device form is the value itself: use groove_ctl_link_create");
+    default:
+      return fail(ctx, "groove_ctl_filter_link_create: unknown control index (a filter link reaches cutoff, q or passband-ripple)");
   }
+  if (!ctl_target_derived(target->kind, control_index))
+    return fail(ctx, "groove_ctl_filter_link_create: the target's kind does not derive its coefficients from that parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)");
+  if (ctl_link_check_sources(ctx, who, src, n_src)) return 1;
   GHIP(ctx, hipSetDevice(ctx->device));
-  groove_ctl_link* l = new groove_ctl_link();
-  l->ctx = ctx; l->source = src[0].source; l->n_src = n_src; l->control_index = control_index; l->target = target;
-  l->src.assign(src, src + n_src);
-  if (hipMalloc(&l->d_lanes, (size_t)3 * n_src * 8) != hipSuccess || hipMalloc(&l->d_value, (size_t)n_src * 4) != hipSuccess ||
-      hipMalloc(&l->d_captured, 4) != hipSuccess) {
-    groove_ctl_link_destroy(l);
-    return fail(ctx, "groove_ctl_link_create: hipMalloc failed");
+  if (!target->d_shadow) { // the first filter link onto this effect: from here on fx_upload_params keeps the shadow beside the coefficients
+    if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
+      target->d_shadow = nullptr;
+      return fail(ctx, "groove_ctl_filter_link_create: hipMalloc failed");
+    }
+    if (fx_acquire_ctx(target) || fx_upload_shadow(target)) return 1;
   }
-  if (hipMemsetAsync(l->d_value, 0, (size_t)n_src * 4, ctx->stream) != hipSuccess || hipMemsetAsync(l->d_captured, 0, 4, ctx->stream) != hipSuccess) {
-    groove_ctl_link_destroy(l);
-    return fail(ctx, "groove_ctl_link_create: hipMemsetAsync failed");
-  }
-  if (ctl_upload_lanes(l)) { groove_ctl_link_destroy(l); return 1; } // (its message stands)
-  ctx->links.push_back(l);
-  *out = l;
-  return 0;
+  return ctl_link_make(ctx, who, src, n_src, target, control_index, true, out);
 }
 int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t frames) {
   if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
@@ -2908,6 +2970,12 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   const uint32_t n = l->n_src;
   const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + (size_t)2 * n);
   const CtlLanes lanes{l->d_lanes, l->d_lanes + n, u, u + n};
+  if (l->derived) {
+    hipLaunchKernelGGL(ctl_filter_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
+                       fx->kind, l->control_index, (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n);
+    GHIP(ctx, hipGetLastError());
+    return 0;
+  }
   const bool as_uint = ctl_target_is_uint(l->control_index);
   hipLaunchKernelGGL(ctl_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
                      as_uint ? nullptr : fx->d_fa, as_uint ? fx->d_ua : nullptr, fx->n);

@@ -428,12 +428,14 @@ class Effect:
 class ControlLink:
     """A controller device linked to one parameter of an Effect, resident on the device (groove_ctl_link): IsController.work
     once per block -> Controllable.control_set_param_by_index of the target, without a host wait.  `sources` is a ctypes array
-    of abi_types.CtlSource, one per target lane or one for all."""
+    of abi_types.CtlSource, one per target lane or one for all.  derived=True makes it a FILTER link (groove_ctl_filter_link_create):
+    onto a filter's cutoff, q or passband-ripple, whose coefficients the link derives on the device."""
 
-    def __init__(self, ctx, sources, target, control_index):
-        self.ctx, self.target, self.n_src = ctx, target, len(sources)
+    def __init__(self, ctx, sources, target, control_index, derived=False):
+        self.ctx, self.target, self.n_src, self.derived = ctx, target, len(sources), derived
         h = C.c_void_p()
-        _lib.check(ctx.L.groove_ctl_link_create(ctx.h, sources, len(sources), target.h, control_index, C.byref(h)), ctx.h)
+        create = ctx.L.groove_ctl_filter_link_create if derived else ctx.L.groove_ctl_link_create
+        _lib.check(create(ctx.h, sources, len(sources), target.h, control_index, C.byref(h)), ctx.h)
         self.h = h
 
     def capture(self, block, frames=None):

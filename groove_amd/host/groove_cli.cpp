@@ -1,7 +1,10 @@
 // groove-cli-hip — offline renderer, the GPU-path counterpart of the reference's `groove-cli`
 // (/root/reference/src/bin/groove-cli.rs:24-53 args, :56-158 main; gated at the reference commit).
 //
-//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--quiet] [--perf] [--debug] FILE...
+//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--quiet] [--perf] [--debug] FILE...
+//
+// --device-filter-links: `controls` onto a filter's cutoff, q or passband-ripple stay on the device (Orchestrator::set_filter_links_on_device),
+// a signal source's among them, which are dropped with a warning otherwise.
 //
 // For each project file: SongSettings::new_from_project_file → instantiate → update_sample_rate(44100)
 // → run_performance(buffer) → (with --wav) send_performance_to_file(<input with .json5/.json → .wav>).
@@ -24,7 +27,7 @@ static std::string wav_name(const std::string& in) {
 }
 
 int main(int argc, char** argv) {
-  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false;
+  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false;
   int device = 0;
   std::string assets = "assets";
   std::vector<std::string> inputs;
@@ -35,11 +38,12 @@ int main(int argc, char** argv) {
     else if (a == "--perf" || a == "-p") perf = true;
     else if (a == "--debug" || a == "-d") debug = true;
     else if (a == "--synthetic-kit") synthetic = true;
+    else if (a == "--device-filter-links") filter_links = true;
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--version" || a == "-v") { std::printf("groove-cli-hip 0.1 (MI355X render path)\n"); return 0; }
     else if (a == "--help" || a == "-h") {
-      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--quiet] [--perf] [--debug] FILE...\n");
+      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--quiet] [--perf] [--debug] FILE...\n");
       return 0;
     } else inputs.push_back(a);
   }
@@ -48,10 +52,15 @@ int main(int argc, char** argv) {
     ProjectDesc desc;
     try { desc = parse_project_file(in, assets); }
     catch (const std::exception& e) { std::fprintf(stderr, "%s: %s\n", in.c_str(), e.what()); return 1; }
-    for (const std::string& w : desc.warnings) std::fprintf(stderr, "Warning: %s\n", w.c_str());
+    for (size_t i = 0; i < desc.warnings.size(); ++i) {
+      bool linked = false; // a control that --device-filter-links links after all is not "dropped"
+      for (const auto& h : desc.held_controls) linked = linked || (filter_links && h.warning == i);
+      if (!linked) std::fprintf(stderr, "Warning: %s\n", desc.warnings[i].c_str());
+    }
     if (debug) std::printf("%s\n", describe(desc).c_str());
     Orchestrator o(device, GROOVE_DEFAULT_SAMPLE_RATE, desc.bpm);
     if (!o.ctx()) { std::fprintf(stderr, "no HIP device: %s (this renderer has no CPU path)\n", o.last_error().c_str()); return 1; }
+    o.set_filter_links_on_device(filter_links);
     if (instantiate(o, desc, assets, synthetic)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (!quiet) std::printf("Performing to queue %s\n", in.c_str());
     const auto t0 = std::chrono::steady_clock::now();

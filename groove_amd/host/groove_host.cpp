@@ -420,6 +420,12 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
     src->add_link({link, target, (uint32_t)idx});
     return 0;
   }
+  if (fx && filter_links_on_device_ && fx_control_device_derived(static_cast<FxEffect*>(te)->kind(), idx)) {
+    groove_ctl_link* link = nullptr;
+    if (groove_ctl_filter_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link)) return fail(groove_last_error(ctx_));
+    src->add_link({link, target, (uint32_t)idx});
+    return 0;
+  }
   if (desc.source == GROOVE_CTL_SRC_SIGNAL) {
     err_ = "link_control: a signal source onto '" + param + "' would need a download per block (the host derives that parameter's device form); dropped";
     return 2;
@@ -728,6 +734,9 @@ int gh_patch_chain_to_main_mixer(void* h, const int* uids, uint32_t n) {
 void gh_unpatch_all(void* h) { ((Orchestrator*)h)->unpatch_all(); }
 void gh_set_render_ahead(void* h, int mode) { ((Orchestrator*)h)->set_render_ahead(mode); }
 void gh_set_fused_direct(void* h, int on) { ((Orchestrator*)h)->set_fused_direct(on != 0); }
+void gh_set_filter_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_filter_links_on_device(on != 0); }
+// groove_debug_info of the orchestrator's context (a JSON object; it waits for the ctx stream).
+int gh_debug_info(void* h, char* out, size_t cap) { return groove_debug_info(((Orchestrator*)h)->ctx(), out, cap); }
 int gh_connect_midi_downstream(void* h, int uid, int channel) { return ((Orchestrator*)h)->connect_midi_downstream((Uid)uid, (uint8_t)channel); }
 int gh_add_timer(void* h, double beats) { return (int)((Orchestrator*)h)->add(std::unique_ptr<Entity>(new Timer(beats))); }
 int gh_add_sequencer(void* h) { return (int)((Orchestrator*)h)->add(std::unique_ptr<Entity>(new Sequencer())); }

@@ -88,11 +88,22 @@ inline int bank_control_index_for_name(const std::string& name) {
   return -1;
 }
 // Can a control link onto this parameter of this kind of effect stay on the device (groove_ctl_link_create: the parameters whose device
-// form IS the value, on the kind whose kernels read them)?
+// form IS the value, on the kind whose kernels read them)?  (A filter's cutoff, q and passband-ripple can too, through a filter link, where
+// the orchestrator has been asked to: Orchestrator::set_filter_links_on_device, fx_control_device_derived below.)
 inline bool fx_control_device_linkable(uint32_t fx_kind, int index) {
   return (index == GROOVE_CTL_FX_CEILING && fx_kind == GROOVE_FX_GAIN) || (index == GROOVE_CTL_FX_BITS && fx_kind == GROOVE_FX_BITCRUSHER) ||
          (index == GROOVE_CTL_FX_ATTENUATION && fx_kind == GROOVE_FX_REVERB) ||
          (index == GROOVE_CTL_FX_THRESHOLD && (fx_kind == GROOVE_FX_COMPRESSOR || fx_kind == GROOVE_FX_LIMITER));
+}
+
+// The parameters a FILTER link reaches (groove_ctl_filter_link_create, which has the last word): cutoff onto the nine filter kinds, q onto the
+// kinds whose formula reads it, passband-ripple onto the 24 dB low-pass.
+inline bool fx_control_device_derived(uint32_t fx_kind, int index) {
+  const bool lp24 = fx_kind == GROOVE_FX_BIQUAD_LP24;
+  const bool bq12 = fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || (fx_kind >= GROOVE_FX_BIQUAD_BP12 && fx_kind <= GROOVE_FX_BIQUAD_HSHELF12);
+  if (index == GROOVE_CTL_FX_CUTOFF) return lp24 || bq12;
+  if (index == GROOVE_CTL_FX_Q) return fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || fx_kind == GROOVE_FX_BIQUAD_AP12;
+  return index == GROOVE_CTL_FX_PASSBAND_RIPPLE && lp24;
 }
 
 // IsInstrument: Generates<StereoSample> + Ticks + HandlesMidi.
@@ -375,6 +386,11 @@ class Orchestrator {
   // 0: linked; 1: error; 2: dropped — a signal source onto a parameter only the host can derive would need a download per block
   // (last_error() says so; the project loader turns it into a warning).
   int link_control(Uid source, Uid target, const std::string& param);
+  // A link onto a filter's cutoff, q or passband-ripple derives the coefficients on the device (groove_ctl_filter_link_create: no host wait)
+  // instead of going through control_effect once per block — and so a signal source onto one of them is linked (0) where it is dropped (2)
+  // with the switch off.  Off by default; it affects the links made after it is set.
+  void set_filter_links_on_device(bool on) { filter_links_on_device_ = on; }
+  bool filter_links_on_device() const { return filter_links_on_device_; }
   // A device-resident link's value for the block at `at_frame`: applied now, or — like control_effect — held back while the controllers
   // are run one block ahead of the effects.
   int control_link(groove_ctl_link* link, uint64_t at_frame);
@@ -420,6 +436,7 @@ class Orchestrator {
   bool performing_ = false;
   int render_ahead_ = 1;
   bool fused_direct_ = true;
+  bool filter_links_on_device_ = false;
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block
   bool deferring_ = false;      // controllers are being run for the NEXT block

@@ -55,6 +55,10 @@ struct ProjectDesc {
   std::vector<Trip> trips;
   std::vector<ControllerDev> controllers;
   std::vector<Control> controls; // the links that resolve (the others are warnings)
+  // signal source -> a filter's cutoff / q / passband-ripple: dropped with a warning (`warning` is its index in `warnings`), and kept here
+  // for an orchestrator that derives filter links on the device (Orchestrator::set_filter_links_on_device): instantiate() links them there
+  struct HeldControl { Control control; size_t warning; };
+  std::vector<HeldControl> held_controls;
   std::vector<std::string> warnings; // the reference eprintln!s and continues (songs.rs:137, 152-156)
 };
 
@@ -84,6 +88,7 @@ bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* s
 // The instantiate() half: devices → entities, patch cables, MIDI routing, tracks → Sequencer,
 // trips → ControlTrip.  With `synthetic_kit` the drumkit uses a generated sample bank instead of
 // <assets>/samples/elphnt.io/707 (the GPU box has no reference assets).
+// With Orchestrator::set_filter_links_on_device(true) set beforehand, the project's held_controls are linked too.
 int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets_root, bool synthetic_kit);
 
 } // namespace groove_host

@@ -26,7 +26,8 @@ def load():
         "gh_add_drumkit": (i, [vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), u32, C.POINTER(C.c_int)]),
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
-        "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_connect_midi_downstream": (i, [vp, i, i]),
+        "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
+        "gh_debug_info": (i, [vp, C.c_char_p, C.c_size_t]), "gh_connect_midi_downstream": (i, [vp, i, i]),
         "gh_add_timer": (i, [vp, d]), "gh_add_sequencer": (i, [vp]),
         "gh_sequencer_insert": (i, [vp, i, i, i, d, d]), "gh_sequencer_set_end": (i, [vp, i, d]),
         "gh_add_control_trip": (i, [vp, i, C.c_char_p, d]), "gh_control_trip_add_step": (i, [vp, i, i, d, d, d]),
@@ -87,6 +88,18 @@ class Orchestrator:
     def set_fused_direct(self, on):
         """Instruments patched straight into the main mixer render fused onto the bus (default) or through their blocks."""
         self.L.gh_set_fused_direct(self.h, 1 if on else 0)
+
+    def set_filter_links_on_device(self, on):
+        """Links made from here on onto a filter's cutoff, q or passband-ripple derive the coefficients on the device (no host wait per
+        block), from an LFO or a signal source; off (the default): an LFO goes through the host once per block, a signal source is dropped."""
+        self.L.gh_set_filter_links_on_device(self.h, 1 if on else 0)
+
+    def debug_info(self):
+        """groove_debug_info of the orchestrator's context, parsed (it waits for the ctx stream)."""
+        import json
+        buf = C.create_string_buffer(1 << 16)
+        self._chk(self.L.gh_debug_info(self.h, buf, len(buf)))
+        return json.loads(buf.value.decode())
 
     def set_render_ahead(self, on):
         """Offline runs: False = block by block, True = instruments one block ahead of the effects whenever the graph allows

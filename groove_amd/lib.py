@@ -92,6 +92,7 @@ SYMBOLS = {
     "groove_fx_set_param": (_i, [_vp, _u32, _u32, _d]),
     "groove_fx_set_params": (_i, [_vp, C.POINTER(T.FxParams), _u32]),
     "groove_ctl_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),
+    "groove_ctl_filter_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),
     "groove_ctl_link_capture": (_i, [_vp, _vp, _u32]),
     "groove_ctl_link_apply": (_i, [_vp, C.c_uint64]),
     "groove_ctl_link_reset": (_i, [_vp]),

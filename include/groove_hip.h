@@ -322,6 +322,18 @@ int groove_fx_set_params(groove_fx* fx, const groove_fx_params* p, uint32_t n);
  * target re-uploads that copy and so overwrites the linked parameter until the link's next apply. */
 int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
                            groove_ctl_link** out);
+/* A FILTER link: the same kind of link onto a parameter that becomes filter coefficients.  Its apply computes the control value as
+ * above, turns it into the parameter by groove_fx_set_param's law (cutoff: 25 * 800^v Hz; q and passband-ripple: 10 v^2 + 0.707,
+ * each rounded to the float groove_fx_params holds), and derives the lane's five or six f64 coefficients ON THE DEVICE from the
+ * effect's per-lane parameter shadow — the formulas of groove_fx_create, one text for both sides (csrc/fx_coef.h) — again with no
+ * host wait and no copy.  The shadow (five floats per lane) is allocated with the first filter link onto an effect; from then on
+ * groove_fx_set_param(s) refresh it with the coefficients, so the staleness rule above holds unchanged, and two links onto one
+ * effect (cutoff and q) see each other's last value in the order of their applies.
+ *   control_index: GROOVE_CTL_FX_CUTOFF onto any of the nine filter kinds, _Q onto low-pass / high-pass / all-pass 12 dB,
+ *   _PASSBAND_RIPPLE onto low-pass 24 dB.  Everything else is refused (_WET included).  The sources are checked as above.
+ * The link it returns is an ordinary one: capture, apply, reset and destroy below. */
+int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                                  groove_ctl_link** out);
 /* TransformsAudio::transform_audio of a SignalPassthroughController: the identity on `block` (it is only read), which keeps, per
  * lane, clamp((L + R) / 2, -1, 1) of frame `frames - 1` for the next groove_ctl_link_apply.  Signal links only; the block has
  * n_src lanes.  Ordered behind whatever fills the block, like every call that reads one. */
