@@ -818,10 +818,9 @@ GROOVE_HD int lfo_class_of(uint32_t waveform, uint32_t routing) {
 }
 // Which kernel instantiation a patch asks for (kernels.h "Workgroup KINDS"): the BASE KIND (LFO mode x retune, in cost order: F32 static,
 // F32 retune, SMOOTH static, SMOOTH retune, exact-F64 static, exact-F64 retune) and the class triple of the block body inside it.  Host
-// and device share the rule (groove_hip.hip welsh_upload_params; tests/emul and tools/library_proportions.py read it through emul.cpp).
+// and device share the rule (welsh_plan.h welsh_plan; tests/emul and tools/library_proportions.py read it through emul.cpp).
 struct WelshParams;
 GROOVE_HD int welsh_base_kind(const WelshParams& p);
-GROOVE_HD bool welsh_base_kind_specialised(int base_kind) { (void)base_kind; return true; } // (round 6: the exact-f64 kinds too; they kept OSC_ANY bodies until then)
 GROOVE_HD void welsh_body_classes(const WelshParams& p, int base_kind, int& cl, int& c1, int& c2);
 template <int CLS>
 GROOVE_HD uint32_t osc_class_wave(uint32_t runtime_waveform) {
@@ -834,10 +833,9 @@ GROOVE_HD int welsh_base_kind(const WelshParams& p) {
   return (mode == LFO_F32 ? 0 : (mode == LFO_F64_SMOOTH ? 2 : 4)) + (welsh_retunes(p) ? 1 : 0);
 }
 GROOVE_HD void welsh_body_classes(const WelshParams& p, int base_kind, int& cl, int& c1, int& c2) {
-  const bool spec = welsh_base_kind_specialised(base_kind);
-  c1 = spec ? osc_class_of((p.flags >> WF_O1_WAVE_SHIFT) & 15u) : (int)OSC_ANY;
-  c2 = spec ? osc_class_of((p.flags >> WF_O2_WAVE_SHIFT) & 15u) : (int)OSC_ANY;
-  cl = spec ? lfo_class_of((p.flags >> WF_LFO_WAVE_SHIFT) & 15u, (p.flags >> WF_ROUTING_SHIFT) & 15u) : (int)OSC_ANY;
+  c1 = osc_class_of((p.flags >> WF_O1_WAVE_SHIFT) & 15u);
+  c2 = osc_class_of((p.flags >> WF_O2_WAVE_SHIFT) & 15u);
+  cl = lfo_class_of((p.flags >> WF_LFO_WAVE_SHIFT) & 15u, (p.flags >> WF_ROUTING_SHIFT) & 15u);
   // the smooth-f64 kernels carry the sine / triangle / any LFO copies only (a square or sawtooth LFO there runs the `any` copy, which has
   // the exact re-seed on the frame of an LFO edge); the F32 and the exact-f64 kernels carry all six
   if ((base_kind == 2 || base_kind == 3) && cl != OSC_SINE && cl != OSC_TRIANGLE) cl = OSC_ANY;

@@ -33,7 +33,7 @@ thread_local std::string g_last_error;
 }
 
 // The lane order of a bank that keeps its voices in another order than the caller gave them (patch-major regrouping,
-// welsh_upload_params): src_lane[caller's lane] = the library's lane.  Shared by the bank and by every block its renders
+// welsh_plan.h welsh_patch_major_order): src_lane[caller's lane] = the library's lane.  Shared by the bank and by every block its renders
 // filled, so that a block outlives a re-grouping (or the bank) with the order its content has.
 struct LaneOrder {
   uint32_t n = 0;
@@ -99,7 +99,6 @@ struct groove_bank {
   uint32_t* d_state = nullptr;
   double* d_cold = nullptr; // welsh: [4][n]; fm: ratio [n]
   WaveDesc* d_waves = nullptr;   // welsh: virtual waves (runs of <= 64 voices sharing a patch)
-  uint32_t n_vwaves = 0;         // 0: the bank runs on the per-lane kernel
   size_t vwaves_cap = 0;
   // welsh, fused path: block pipeline (render_mix_pipelined).  Two slots of partial rows / segment sums and
   // the events that order slot reuse: a base kind's render of block b+2 waits for the reduce of block b.
@@ -115,21 +114,17 @@ struct groove_bank {
   int stream_slot = 0; // side stream of a single-kernel bank (FM, sampler, per-lane Welsh) in the asynchronous fused path
   bool ctx_touched = true; // the ctx stream has worked on this bank's state since its last asynchronous render waited for it
   int side_mode = 0;    // which side streams carried this bank's last asynchronous work: 0 none, 1 one per base kind, 2 stream_slot
-  // welsh: lane permutation.  A bank whose patches are interleaved voice by voice is kept patch-major inside
-  // the library (params, state, cold values in INTERNAL lane order) so that it runs on the wave-uniform kernels;
-  // perm[internal lane] = caller's voice index, inv = its inverse.  Empty = identity.
-  std::vector<uint32_t> perm, inv;
-  std::shared_ptr<LaneOrder> order; // device copy of inv, shared with the blocks this bank's renders fill (groove_block: lazy lane order)
+  // welsh: what the launches read of the bank's plan (welsh_plan.h): the lane permutation, the number of virtual waves (0: the per-lane
+  // kernel), the time-parallel form's two conditions, the slice lengths of the sorted lists and the mix kernel's sections of the striped ones
+  WelshLayout plan;
+  std::shared_ptr<LaneOrder> order; // device copy of plan.inv, shared with the blocks this bank's renders fill (groove_block: lazy lane order)
   uint8_t* d_wg_cls = nullptr;   // welsh: oscillator class pair of each entry of d_wg_list
-  bool tp_full_coef = false;     // welsh: some voice routes the LFO to the resonance (welsh_tp_kernel<.., FULL_COEF>)
-  bool tp_pairs = false;         // welsh: every pair of adjacent voices (2i, 2i + 1) shares a patch (welsh_tp_kernel<.., VPW = 2>)
   uint8_t* d_wg_base = nullptr;  // welsh: base kind of each entry of d_wg_list (the all-kinds kernel of small banks)
   uint8_t* d_wg_f32 = nullptr;   // welsh: 1 where the entry's patches carry WF_FILTER_F32 (the fused per-kind kernels)
-  uint32_t mix_off[3] = {}, mix_cnt[3] = {}; // welsh: the MIX kernel's three sections of the lists (kernels.h): entries [wg_list_cap + mix_off[s], + mix_cnt[s]) of all four arrays — the
-                                             // class-specialised workgroups of the kind-sorted list taken with a stride of three, each section kind-sorted itself
-  uint32_t* d_wg_list = nullptr; // welsh: workgroup ids (groups of 4 virtual waves) sorted by kind (kernels.h)
+  // welsh: workgroup ids (groups of 4 virtual waves) sorted by kind (kernels.h).  All four d_wg_ arrays hold 2 * wg_list_cap entries: plan.sorted
+  // from entry 0, plan.striped — the mix kernel's sections, [wg_list_cap + mix_off[s], + mix_cnt[s]) — from entry wg_list_cap
+  uint32_t* d_wg_list = nullptr;
   size_t wg_list_cap = 0;
-  uint32_t wgs_of_kind[kWgKinds] = {};  // slice lengths of d_wg_list, in kind order
   float* d_pcm = nullptr;   // sampler bank
   groove_note_event* d_ev[2] = {nullptr, nullptr};
   // pinned staging of queued note events, two slots in rotation: flush_events hands the events to the ctx
@@ -140,7 +135,6 @@ struct groove_bank {
   hipEvent_t ev_staged[2] = {nullptr, nullptr};
   bool staged[2] = {false, false};
   int ev_slot = 0;
-  groove_block* scratch = nullptr; // for render_mix
   std::vector<groove_note_event> pending;
   InlineEvents inline_ev{};  // sampler: this block's events, to ride in the next time-parallel render's arguments (flush_events)
   std::vector<groove_welsh_params> welsh;
@@ -501,27 +495,8 @@ int upload_soa(groove_ctx* ctx, uint32_t* dst, const std::vector<T>& aos) {
 }
 inline uint32_t blocks_for(size_t items) { return (uint32_t)((items + kThreads - 1) / kThreads); }
 
-// Welsh: derive + upload parameters only (SoA, cold values, per-wave table, workgroup kinds).
-// Number of virtual waves (runs of <= 64 equal parameter records) the lane order `at(i)` gives.
-template <class At>
-size_t count_virtual_waves(const std::vector<WelshParams>& P, uint32_t n, At&& at) {
-  size_t waves = 0;
-  for (uint32_t i = 0; i < n;) {
-    uint32_t e = i + 1;
-    while (e < n && e - i < 64 && std::memcmp(&P[at(e)], &P[at(i)], sizeof(WelshParams)) == 0) ++e;
-    ++waves;
-    i = e;
-  }
-  return waves;
-}
-inline bool runs_are_long(size_t virtual_waves, uint32_t n) {
-  // Use the scalar-parameter kernels when the runs are long (at most 1.5x as many virtual waves as
-  // physical ones), or when the bank is so small that even one short run per wave leaves the machine
-  // (1,024 SIMDs) under-filled: there a partly filled fast wave beats a full slow one.
-  const uint32_t phys_waves = (n + 63) / 64;
-  return !(virtual_waves > (size_t)phys_waves + phys_waves / 2 + 8 && virtual_waves > 2048);
-}
-// `regroup`: the state is (being) reset, so the lane order may be chosen afresh.
+// Welsh: derive + upload parameters only (SoA, cold values, per-wave table, workgroup lists): derive -> flag -> order -> plan
+// (welsh_plan.h) -> grow -> upload.  `regroup`: the state is (being) reset, so the lane order may be chosen afresh.
 int welsh_upload_params(groove_bank* b, bool regroup) {
   groove_ctx* ctx = b->ctx;
   const double sr = ctx->sr;
@@ -545,158 +520,41 @@ int welsh_upload_params(groove_bank* b, bool regroup) {
       if (it->second) Pext[v].flags |= WF_FILTER_F32;
     }
   }
+  WelshPlan plan = welsh_plan(Pext, Cext, regroup ? welsh_patch_major_order(Pext) : std::move(b->plan.perm));
+  b->plan = std::move(static_cast<WelshLayout&>(plan)); // what the launches read stays with the bank; the arrays of `plan` are uploaded below
   if (regroup) {
-    b->perm.clear(); b->inv.clear();
-    if (!runs_are_long(count_virtual_waves(Pext, n, [](uint32_t i) { return i; }), n)) {
-      // patches interleaved voice by voice: try the patch-major order (stable sort by a hash of the record)
-      std::vector<uint64_t> h(n);
-      for (uint32_t v = 0; v < n; ++v) {
-        uint64_t x = 1469598103934665603ull;
-        const unsigned char* bytes = reinterpret_cast<const unsigned char*>(&Pext[v]);
-        for (size_t k = 0; k < sizeof(WelshParams); ++k) { x ^= bytes[k]; x *= 1099511628211ull; }
-        h[v] = x;
-      }
-      std::vector<uint32_t> order(n);
-      for (uint32_t v = 0; v < n; ++v) order[v] = v;
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) { return h[a] < h[c]; });
-      if (runs_are_long(count_virtual_waves(Pext, n, [&](uint32_t i) { return order[i]; }), n)) {
-        b->perm = std::move(order);
-        b->inv.resize(n);
-        for (uint32_t i = 0; i < n; ++i) b->inv[b->perm[i]] = i;
-      }
-    }
     b->order.reset(); // blocks filled under the old order keep it alive for as long as they hold that content
-    if (!b->perm.empty()) {
+    if (!b->plan.perm.empty()) {
       auto o = std::make_shared<LaneOrder>();
       o->n = n;
       GHIP(ctx, hipMalloc(&o->d_src_lane, (size_t)n * sizeof(uint32_t)));
-      GHIP(ctx, ctx_memcpy(ctx, o->d_src_lane, b->inv.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+      GHIP(ctx, ctx_memcpy(ctx, o->d_src_lane, b->plan.inv.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
       b->order = std::move(o);
     }
   }
-  // everything below is in INTERNAL lane order
-  std::vector<WelshParams> P(n);
-  std::vector<double> cold((size_t)4 * n);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t v = b->perm.empty() ? i : b->perm[i];
-    P[i] = Pext[v];
-    const WelshCold& c = Cext[v];
-    cold[i] = c.tune1; cold[(size_t)n + i] = c.tune2; cold[(size_t)2 * n + i] = c.fixed1; cold[(size_t)3 * n + i] = c.fixed2;
-  }
-  if (upload_soa(ctx, b->d_params, P)) return 1;
-  GHIP(ctx, ctx_memcpy(ctx, b->d_cold, cold.data(), cold.size() * 8, hipMemcpyHostToDevice));
-  b->tp_pairs = true; // time-parallel form, two voices per wavefront: voices 2i and 2i + 1 share their parameter words
-  for (uint32_t i = 0; i + 1 < n && b->tp_pairs; i += 2) b->tp_pairs = std::memcmp(&P[i], &P[i + 1], sizeof(WelshParams)) == 0;
-  b->tp_full_coef = false; // time-parallel form: a voice with the resonance routing keeps six f64 coefficients per frame (welsh_tp.h)
-  for (uint32_t i = 0; i < n; ++i) if (P[i].flags & WF_LFO_RESO) { b->tp_full_coef = true; break; } // (WF_COEF_WIDE patches: from the tangent like the rest, round 6)
-  // Virtual waves: maximal runs of consecutive voices with identical parameter words, cut at 64.
-  std::vector<WaveDesc> W;
-  W.reserve((size_t)n / 64 + 64);
-  for (uint32_t v = 0; v < n;) {
-    uint32_t e = v + 1;
-    while (e < n && e - v < 64 && std::memcmp(&P[e], &P[v], sizeof(WelshParams)) == 0) ++e;
-    WaveDesc d;
-    d.p = P[v]; d.vbase = v; d.count = e - v;
-    W.push_back(d);
-    v = e;
-  }
-  for (uint32_t& c : b->wgs_of_kind) c = 0;
-  // Otherwise (every voice its own patch, even patch-major) the per-lane kernel serves the whole bank.
-  if (!runs_are_long(W.size(), n)) {
-    b->n_vwaves = 0;
-    return 0;
-  }
-  // A workgroup runs in ONE instantiation (kernels.h, "Workgroup KINDS"), so it is built from waves that
-  // ask for the same one: the waves are ordered by the kind they need and every kind's last workgroup is
-  // filled up with empty waves (count 0).  (Cutting the run order into fours made every workgroup of a
-  // small many-patch bank a mixture, which runs in the most demanding base kind with the run-time
-  // waveform switches: config #2's 32 waves took 0.21 ms per block where their slowest patch needs 0.16.)
-  auto kind_of_wave = [](const WelshParams& p) -> uint16_t {
-    const int base = welsh_base_kind(p); // == wg_base_kind_of(welsh_lfo_mode(p), welsh_retunes(p)); dsp_core.h
-    int cl, c1, c2;
-    welsh_body_classes(p, base, cl, c1, c2);
-    return (uint16_t)wg_kind_of(base, cl, c1, c2);
-  };
-  std::vector<uint16_t> kind; // per workgroup
-  std::vector<uint8_t> f32_of; // per workgroup: its waves' patches carry WF_FILTER_F32 (a workgroup is uniform in it too: sort key bit 0)
-  {
-    std::vector<uint32_t> wave_kind(W.size()); // (kind << 1) | fp32-filter flag
-    std::vector<uint32_t> order(W.size());
-    for (uint32_t w = 0; w < W.size(); ++w) { wave_kind[w] = ((uint32_t)kind_of_wave(W[w].p) << 1) | ((W[w].p.flags & WF_FILTER_F32) ? 1u : 0u); order[w] = w; }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) { return wave_kind[a] < wave_kind[c]; });
-    std::vector<WaveDesc> packed;
-    packed.reserve(W.size() + (size_t)kWaves * 64);
-    for (size_t i = 0; i < order.size();) {
-      size_t e = i;
-      while (e < order.size() && wave_kind[order[e]] == wave_kind[order[i]]) ++e;
-      for (size_t j = i; j < e; ++j) {
-        if ((j - i) % kWaves == 0) { kind.push_back((uint16_t)(wave_kind[order[i]] >> 1)); f32_of.push_back((uint8_t)(wave_kind[order[i]] & 1u)); }
-        packed.push_back(W[order[j]]);
-      }
-      while (packed.size() % kWaves) { // empty waves: no lane active, the first wave's voice as the shadow address
-        WaveDesc pad = W[order[i]];
-        pad.count = 0;
-        packed.push_back(pad);
-      }
-      i = e;
-    }
-    W.swap(packed);
-  }
-  b->n_vwaves = (uint32_t)W.size();
-  const uint32_t wgs = b->n_vwaves / kWaves;
-  std::vector<uint32_t> wg_list(wgs);
-  std::vector<uint8_t> wg_cls(wgs), wg_base(wgs), wg_f32(wgs);
-  {
-    std::vector<uint32_t> at(kWgKinds + 1, 0);
-    for (uint16_t k : kind) b->wgs_of_kind[k] += 1;
-    for (int k = 0; k < kWgKinds; ++k) at[k + 1] = at[k] + b->wgs_of_kind[k];
-    for (uint32_t g = 0; g < wgs; ++g) {
-      const uint32_t slot = at[kind[g]]++;
-      wg_list[slot] = g;
-      wg_cls[slot] = (uint8_t)(kind[g] % kClassCombos);
-      wg_base[slot] = (uint8_t)(kind[g] / kClassCombos);
-      wg_f32[slot] = f32_of[g];
-    }
-  }
-  if (b->vwaves_cap < W.size()) {
+  if (upload_soa(ctx, b->d_params, plan.records)) return 1;
+  GHIP(ctx, ctx_memcpy(ctx, b->d_cold, plan.cold.data(), plan.cold.size() * 8, hipMemcpyHostToDevice));
+  if (plan.waves.empty()) return 0; // the per-lane kernel reads no wave and no list
+  const size_t wgs = plan.sorted.list.size(), n_spec = plan.striped.list.size();
+  if (b->vwaves_cap < plan.waves.size()) {
     if (b->d_waves) GHIP(ctx, hipFree(b->d_waves));
-    b->vwaves_cap = W.size() + W.size() / 8 + 16;
+    b->vwaves_cap = plan.waves.size() + plan.waves.size() / 8 + 16;
     GHIP(ctx, hipMalloc(&b->d_waves, b->vwaves_cap * sizeof(WaveDesc)));
   }
-  if (b->wg_list_cap < wgs) {
-    if (b->d_wg_list) GHIP(ctx, hipFree(b->d_wg_list));
-    b->wg_list_cap = wgs + wgs / 8 + 16;
-    // (twice the capacity: the kind-sorted lists in the first half, the mix kernel's striped copy of them in the second)
-    GHIP(ctx, hipMalloc(&b->d_wg_list, 2 * b->wg_list_cap * sizeof(uint32_t)));
-    if (b->d_wg_cls) GHIP(ctx, hipFree(b->d_wg_cls));
-    GHIP(ctx, hipMalloc(&b->d_wg_cls, 2 * b->wg_list_cap));
-    if (b->d_wg_base) GHIP(ctx, hipFree(b->d_wg_base));
-    GHIP(ctx, hipMalloc(&b->d_wg_base, 2 * b->wg_list_cap));
-    if (b->d_wg_f32) GHIP(ctx, hipFree(b->d_wg_f32));
-    GHIP(ctx, hipMalloc(&b->d_wg_f32, 2 * b->wg_list_cap));
-  }
-  GHIP(ctx, ctx_memcpy(ctx, b->d_waves, W.data(), W.size() * sizeof(WaveDesc), hipMemcpyHostToDevice));
-  GHIP(ctx, ctx_memcpy(ctx, b->d_wg_list, wg_list.data(), (size_t)wgs * sizeof(uint32_t), hipMemcpyHostToDevice));
-  GHIP(ctx, ctx_memcpy(ctx, b->d_wg_cls, wg_cls.data(), wgs, hipMemcpyHostToDevice));
-  GHIP(ctx, ctx_memcpy(ctx, b->d_wg_base, wg_base.data(), wgs, hipMemcpyHostToDevice));
-  GHIP(ctx, ctx_memcpy(ctx, b->d_wg_f32, wg_f32.data(), wgs, hipMemcpyHostToDevice));
-  { // the mix kernel's sections: slots s, s + 3, s + 6 ... of the class-specialised part of the sorted list (the exact-f64 kinds, last in it, keep their own kernels)
-    uint32_t n_spec = 0;
-    for (int k = 0; k < 4 * kClassCombos; ++k) n_spec += b->wgs_of_kind[k];
-    std::vector<uint32_t> m_list(n_spec);
-    std::vector<uint8_t> m_cls(n_spec), m_base(n_spec), m_f32(n_spec);
-    uint32_t at = 0;
-    for (uint32_t sec = 0; sec < 3; ++sec) {
-      b->mix_off[sec] = at;
-      for (uint32_t g = sec; g < n_spec; g += 3, ++at) { m_list[at] = wg_list[g]; m_cls[at] = wg_cls[g]; m_base[at] = wg_base[g]; m_f32[at] = wg_f32[g]; }
-      b->mix_cnt[sec] = at - b->mix_off[sec];
+  GHIP(ctx, ctx_memcpy(ctx, b->d_waves, plan.waves.data(), plan.waves.size() * sizeof(WaveDesc), hipMemcpyHostToDevice));
+  // The four lists, each of twice the capacity: the kind-sorted list from entry 0, the mix kernel's striped copy of it from wg_list_cap.
+  const bool grow = b->wg_list_cap < wgs;
+  if (grow) b->wg_list_cap = wgs + wgs / 8 + 16;
+  struct { void** d; const void* sorted; const void* striped; size_t entry; } lists[4] = {
+      {(void**)&b->d_wg_list, plan.sorted.list.data(), plan.striped.list.data(), sizeof(uint32_t)}, {(void**)&b->d_wg_cls, plan.sorted.cls.data(), plan.striped.cls.data(), 1},
+      {(void**)&b->d_wg_base, plan.sorted.base.data(), plan.striped.base.data(), 1}, {(void**)&b->d_wg_f32, plan.sorted.f32.data(), plan.striped.f32.data(), 1}};
+  for (auto& l : lists) {
+    if (grow) {
+      if (*l.d) GHIP(ctx, hipFree(*l.d));
+      GHIP(ctx, hipMalloc(l.d, 2 * b->wg_list_cap * l.entry));
     }
-    if (n_spec) {
-      GHIP(ctx, ctx_memcpy(ctx, b->d_wg_list + b->wg_list_cap, m_list.data(), (size_t)n_spec * sizeof(uint32_t), hipMemcpyHostToDevice));
-      GHIP(ctx, ctx_memcpy(ctx, b->d_wg_cls + b->wg_list_cap, m_cls.data(), n_spec, hipMemcpyHostToDevice));
-      GHIP(ctx, ctx_memcpy(ctx, b->d_wg_base + b->wg_list_cap, m_base.data(), n_spec, hipMemcpyHostToDevice));
-      GHIP(ctx, ctx_memcpy(ctx, b->d_wg_f32 + b->wg_list_cap, m_f32.data(), n_spec, hipMemcpyHostToDevice));
-    }
+    GHIP(ctx, ctx_memcpy(ctx, *l.d, l.sorted, wgs * l.entry, hipMemcpyHostToDevice));
+    if (n_spec) GHIP(ctx, ctx_memcpy(ctx, (char*)*l.d + b->wg_list_cap * l.entry, l.striped, n_spec * l.entry, hipMemcpyHostToDevice));
   }
   return 0;
 }
@@ -775,7 +633,7 @@ int flush_events(groove_bank* b, bool inline_ok = false) {
   }
   if (b->pending.empty()) return 0;
   groove_ctx* ctx = b->ctx;
-  if (inline_ok && b->kind == BANK_SAMPLER && b->inv.empty() && b->pending.size() <= kInlineEvents) {
+  if (inline_ok && b->kind == BANK_SAMPLER && b->plan.inv.empty() && b->pending.size() <= kInlineEvents) {
     bool sorted = b->pending[0].voice != GROOVE_ALL_VOICES;
     for (size_t i = 1; sorted && i < b->pending.size(); ++i) sorted = b->pending[i].voice != GROOVE_ALL_VOICES && b->pending[i].voice > b->pending[i - 1].voice;
     if (sorted) {
@@ -803,9 +661,9 @@ int flush_events(groove_bank* b, bool inline_ok = false) {
   // caller's voice index -> internal lane, into a copy: a failure below leaves `pending` as it was queued,
   // so the next flush maps it exactly once
   std::vector<groove_note_event> ev = b->pending;
-  if (!b->inv.empty())
+  if (!b->plan.inv.empty())
     for (groove_note_event& e : ev)
-      if (e.voice != GROOVE_ALL_VOICES) e.voice = b->inv[e.voice];
+      if (e.voice != GROOVE_ALL_VOICES) e.voice = b->plan.inv[e.voice];
   // Device and pinned host staging, two slots each in rotation: the events of this flush are handed to the
   // stream and the call returns without a host synchronisation.
   const int hs = b->ev_slot;
@@ -1638,7 +1496,6 @@ int groove_bank_destroy(groove_bank* b) {
   }
   auto it = std::find(ctx->banks.begin(), ctx->banks.end(), b);
   if (it != ctx->banks.end()) ctx->banks.erase(it);
-  if (b->scratch) groove_block_destroy(b->scratch);
   for (int k = 0; k < 2; ++k) { if (b->h_ev[k]) (void)hipHostFree(b->h_ev[k]); if (b->ev_staged[k]) (void)hipEventDestroy(b->ev_staged[k]); }
   (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
   delete b;
@@ -1695,7 +1552,7 @@ static bool use_tp(const groove_bank* b, uint32_t frames) {
     // two voices per wavefront move the crossover with the role-split kernel up by three eighths (measured, round 3: 18,432
     // voices 0.069 ms per block against 0.083, 22,528 0.080 against 0.084, 24,576 0.084 against 0.083)
     const uint32_t tmax = b->ctx->tp_max_voices;
-    const bool pairs = b->tp_pairs && b->ctx->tp_vpw2_min_voices && b->n >= b->ctx->tp_vpw2_min_voices;
+    const bool pairs = b->plan.tp_pairs && b->ctx->tp_vpw2_min_voices && b->n >= b->ctx->tp_vpw2_min_voices;
     return b->n <= (pairs ? tmax + (uint32_t)std::min<uint64_t>((uint64_t)tmax * 3 / 8, 0x40000000u) : tmax);
   }
   if (b->kind == BANK_FM) return b->n <= b->ctx->fm_tp_max_voices; // no filter scan: far cheaper per voice than a Welsh voice
@@ -1707,7 +1564,7 @@ static uint32_t tp_vpw(const groove_bank* b) { // voices per wavefront of the ti
     const uint32_t m = b->ctx->fm_tp_vpw4_min_voices;
     return (m && b->n >= m) ? 4u : 1u;
   }
-  return (b->kind == BANK_WELSH && b->tp_pairs && b->ctx->tp_vpw2_min_voices && b->n >= b->ctx->tp_vpw2_min_voices) ? 2u : 1u;
+  return (b->kind == BANK_WELSH && b->plan.tp_pairs && b->ctx->tp_vpw2_min_voices && b->n >= b->ctx->tp_vpw2_min_voices) ? 2u : 1u;
 }
 // ---- which kernel form a bank takes for a block, and the launches of each form
 // THE form decision: the entry points below, fused_rows, use_split and groove_bank_kernel_form all ask here.
@@ -1723,43 +1580,32 @@ static Form form_of(const groove_bank* b, uint32_t frames) {
   if (use_tp(b, frames)) return Form::TimeParallel;
   if (b->kind == BANK_FM) return Form::FmSerial;
   if (b->kind == BANK_SAMPLER) return Form::SamplerSerial;
-  if (b->n_vwaves == 0) return Form::WelshPerLane;
-  return b->n_vwaves < b->ctx->pipeline_min_waves ? Form::WelshSmallUniform : Form::WelshBigUniform;
+  if (b->plan.n_vwaves == 0) return Form::WelshPerLane;
+  return b->plan.n_vwaves < b->ctx->pipeline_min_waves ? Form::WelshSmallUniform : Form::WelshBigUniform;
 }
 // rows of partial[][2][frames] a bank's fused render writes: one per workgroup of the form's launch(es)
 static uint32_t fused_rows(const groove_bank* b, Form form) {
   switch (form) {
     case Form::TimeParallel: return b->kind == BANK_SAMPLER ? sampler_tp_workgroups(b->n) : b->kind == BANK_WELSH ? welsh_tp_grid(b->n, tp_vpw(b)) : welsh_tp_workgroups(b->n, tp_vpw(b));
-    case Form::WelshSmallUniform: case Form::WelshBigUniform: return (b->n_vwaves + kWaves - 1) / kWaves;
+    case Form::WelshSmallUniform: case Form::WelshBigUniform: return (b->plan.n_vwaves + kWaves - 1) / kWaves;
     default: return blocks_for(b->n);
   }
 }
 // A small-uniform bank's launch is role-split (welsh_split.h) when the bank is mid-size and the block long enough.
 static bool use_split(const groove_bank* b, Form form, uint32_t frames) {
-  return form == Form::WelshSmallUniform && b->n_vwaves <= b->ctx->split_max_waves && frames >= 2 * kSplitChunk;
+  return form == Form::WelshSmallUniform && b->plan.n_vwaves <= b->ctx->split_max_waves && frames >= 2 * kSplitChunk;
 }
 // The one argument block of the wave-uniform Welsh kernels: entries [wg_off, wg_off + n_wgs) of the bank's workgroup lists.
 static UniformArgs uniform_args(const groove_bank* b, float* out, float* rows, size_t wg_off, size_t chs, uint32_t frames, uint32_t n_wgs) {
-  UniformArgs a{b->d_waves, b->d_state, out, rows, b->d_wg_list + wg_off, b->d_wg_cls + wg_off, b->d_wg_f32 + wg_off, chs, render_consts_of(b->ctx), b->n_vwaves, b->n, frames, n_wgs, TpPrev{}};
+  UniformArgs a{b->d_waves, b->d_state, out, rows, b->d_wg_list + wg_off, b->d_wg_cls + wg_off, b->d_wg_f32 + wg_off, chs, render_consts_of(b->ctx), b->plan.n_vwaves, b->n, frames, n_wgs, TpPrev{}};
   a.diag = b->ctx->d_diag;
 #ifdef GROOVE_HEARTBEAT
   a.heartbeat = b->ctx->hb;
 #endif
   return a;
 }
-// The pieces of a wave-uniform bank: the per-base-kind slices of its kind-sorted workgroup list (kernels.h, "Workgroup KINDS":
-// the four class-specialised base kinds first, n_spec workgroups in all, then the two exact-f64 ones) ...
-struct KindSlices { uint32_t count[kBaseKinds] = {}, offset[kBaseKinds] = {}, n_spec = 0; };
-static KindSlices kind_slices(const groove_bank* b) {
-  KindSlices p;
-  for (uint32_t base = 0, at = 0; base < (uint32_t)kBaseKinds; ++base) {
-    p.offset[base] = at;
-    for (int c = 0; c < kClassCombos; ++c) p.count[base] += b->wgs_of_kind[base * kClassCombos + c];
-    at += p.count[base];
-  }
-  p.n_spec = p.offset[4];
-  return p;
-}
+// The pieces of a wave-uniform bank: the per-base-kind slices of its kind-sorted workgroup list (welsh_plan.h KindSlices) ...
+static KindSlices kind_slices(const groove_bank* b) { return kind_slices(b->plan.wgs_of_kind); }
 // One base kind's uniform Welsh kernel over `a`'s workgroups on stream `st`: every base kind has class-specialised bodies
 // (round 6: the two exact-f64 kinds too), one translation unit each (csrc/welsh_class.hip).
 static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr) {
@@ -1772,10 +1618,10 @@ static void launch_kind_slice(const groove_bank* b, const KindSlices& p, int k, 
   launch_welsh_kind(k, uniform_args(b, out, rows, p.offset[k], chs, frames, p.count[k]), st, fused, done);
 }
 // ... and the three sections of the MIX kernel (kernels.h; round 6): the class-specialised workgroups in three launches, each over a
-// third of them — the section's entries of the striped copies of all four lists (welsh_upload_params).
+// third of them — the section's entries of the striped copies of all four lists (welsh_plan.h).
 static void launch_mix_section(const groove_bank* b, int sec, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
-  const size_t o = b->wg_list_cap + b->mix_off[sec];
-  const UniformArgs a = uniform_args(b, out, rows, o, chs, frames, b->mix_cnt[sec]);
+  const size_t o = b->wg_list_cap + b->plan.mix_off[sec];
+  const UniformArgs a = uniform_args(b, out, rows, o, chs, frames, b->plan.mix_cnt[sec]);
   if (fused) launch_welsh_uniform_mix(a, b->d_wg_base + o, st, done);
   else launch_welsh_uniform_mix_unfused(a, b->d_wg_base + o, st, done);
 }
@@ -1816,7 +1662,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
       if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
       else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
-      else { a.full_coef = b->tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
+      else { a.full_coef = b->plan.tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
       break;
     }
     case Form::WelshSmallUniform: {
@@ -1978,7 +1824,7 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
       end(k);
     }
     for (int sec = 2; sec >= 0; --sec) {
-      if (!b->mix_cnt[sec]) continue;
+      if (!b->plan.mix_cnt[sec]) continue;
       hipStream_t st = begin(sec);
       launch_mix_section(b, sec, false, chs, dst, rows, frames, st);
       end(sec);
@@ -2078,7 +1924,7 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
   uint32_t launches = 0;
   if (uniform) {
     p = kind_slices(b);
-    for (int sec = 0; sec < 3; ++sec) if (b->mix_cnt[sec]) launches |= 1u << sec; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds; 3: nothing
+    for (int sec = 0; sec < 3; ++sec) if (b->plan.mix_cnt[sec]) launches |= 1u << sec; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds; 3: nothing
     for (int k = 4; k < kBaseKinds; ++k) if (p.count[k]) launches |= 1u << k;
   } else if (rows) {
     launches = 1u << b->stream_slot; // one kernel, on this bank's side stream (the loop below runs once)
@@ -2249,7 +2095,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
     if (!b) return fail(ctx, "groove_banks_render_mix_deferred: NULL bank");
     if (b->ctx != ctx) return fail(ctx, "groove_banks_render_mix_deferred: a bank of another ctx");
     const int k = b->kind == BANK_WELSH ? 0 : b->kind == BANK_FM ? 1 : 2;
-    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->tp_full_coef)) ok = false;
+    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef)) ok = false;
     of_kind[k] = b;
   }
   TpMixedArgs m{};
@@ -2313,7 +2159,7 @@ int groove_bank_render_mix(groove_bank* b, uint32_t frames, float* bus_dev, int 
   const bool force = ctx->pipeline_min_waves <= 1;
   const Form form = form_of(b, frames);
   // (a Welsh bank past the threshold that still renders time-parallel — the knobs can make one — has always walked this way too)
-  const bool big = form == Form::WelshBigUniform || (form == Form::TimeParallel && b->kind == BANK_WELSH && b->n_vwaves >= ctx->pipeline_min_waves);
+  const bool big = form == Form::WelshBigUniform || (form == Form::TimeParallel && b->kind == BANK_WELSH && b->plan.n_vwaves >= ctx->pipeline_min_waves);
   if (big || force || ctx->banks.size() > 1) return render_mix_pipelined(b, frames, bus_dev, accumulate);
   if (ctx_join(ctx)) return 1; // earlier pipelined blocks of this bank may still be running on the side streams
   const uint32_t rows = fused_rows(b, form);
@@ -2372,13 +2218,13 @@ int groove_bank_download_state(groove_bank* b, uint32_t* host_words) {
   if (flush_events(b)) return 1;
   if (ctx_join(ctx)) return 1;
   GHIP(ctx, ctx_wait(ctx));
-  if (b->perm.empty()) {
+  if (b->plan.perm.empty()) {
     GHIP(ctx, ctx_memcpy(ctx, host_words, b->d_state, (size_t)b->sw * b->n * 4, hipMemcpyDeviceToHost));
   } else { // internal lane order -> caller's voice order
     std::vector<uint32_t> tmp((size_t)b->sw * b->n);
     GHIP(ctx, ctx_memcpy(ctx, tmp.data(), b->d_state, tmp.size() * 4, hipMemcpyDeviceToHost));
     for (uint32_t w = 0; w < b->sw; ++w)
-      for (uint32_t i = 0; i < b->n; ++i) host_words[(size_t)w * b->n + b->perm[i]] = tmp[(size_t)w * b->n + i];
+      for (uint32_t i = 0; i < b->n; ++i) host_words[(size_t)w * b->n + b->plan.perm[i]] = tmp[(size_t)w * b->n + i];
   }
   return 0;
 }

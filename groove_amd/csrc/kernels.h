@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 #include "dsp_core.h"
 #include "derive.h"
+#include "welsh_plan.h"
 #include "diag.h"
 
 namespace groove {
@@ -84,6 +85,7 @@ __device__ __forceinline__ void soa_store(uint32_t* __restrict__ buf, uint32_t n
    frame loop of its own for the table frames in more bodies than below, builds without the look-aheads — are described in docs/HISTORY.md.) */
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
+static_assert(kWaves == kPlanWaves, "a workgroup of the plan (welsh_plan.h) is one workgroup of the kernels");
 // Which entry of the kind-sorted workgroup list (cheapest base kind first) workgroup blockIdx.x of a launch takes: from the END.
 // The most expensive kinds start first (longest-processing-time-first), so that a launch of more than one round of workgroups does
 // not end with its longest workgroups alone on the chip.  Same results (a workgroup's voices do not care when they run); measured
@@ -254,7 +256,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
 //
 // Why ACTIVE lanes only (the stall of rounds 2-3).  A lane that is not active carries a SHADOW of some
 // voice's state record so that its loads have an address: in a partly filled wave its own wave's first voice, in a PADDING
-// wave (count 0: welsh_upload_params fills every kind's last workgroup up to four waves) the first voice of the kind's first
+// wave (count 0: welsh_plan fills every kind's last workgroup up to four waves) the first voice of the kind's first
 // wave — a voice that another workgroup of the SAME launch owns, and stores at the end of its block while this workgroup, in a
 // later round of the grid, may be loading it.  The shadow can therefore be a torn record: after a note-on an instant-attack
 // voice holds (ATTACK, n 0, N 0), one block later (SUSTAIN, n, N 2^32-1), and the mixture (SUSTAIN, N 0) is a plateau that is
@@ -604,23 +606,10 @@ __global__ __launch_bounds__(kThreads) void welsh_render_kernel(
 //     a base kind need about the same registers, so the kernel's budget fits them all.  (One kernel
 //     per class pair was tried too: 32 small launches per block do not run concurrently - the
 //     hardware queues are few - and the block took 1.5x as long.)
-// The host builds every workgroup from waves that need the SAME kind (welsh_upload_params: the wave
+// The host builds every workgroup from waves that need the SAME kind (welsh_plan.h welsh_plan: the wave
 // descriptors are ordered by kind, a kind's last workgroup is filled up with empty waves), so no
-// wave runs in a more demanding instantiation than its patch asks for.
-struct WaveDesc {
-  WelshParams p;
-  uint32_t vbase, count;
-};
-constexpr int kBaseKinds = 6;                                     // LFO mode x retune
-constexpr int kClassCombos = LFO_CLASSES * OSC_CLASSES * OSC_CLASSES;  // (LFO class, oscillator 1 class, oscillator 2 class)
-constexpr int kWgKinds = kBaseKinds * kClassCombos;                    // sort key of the workgroup list
-__host__ __device__ constexpr int wg_base_kind_of(int lfo_mode, bool retune) {
-  // cost order (cheap to expensive): F32 static, F32 retune, SMOOTH static, SMOOTH retune, F64 static, F64 retune
-  return (lfo_mode == LFO_F32 ? 0 : (lfo_mode == LFO_F64_SMOOTH ? 2 : 4)) + (retune ? 1 : 0);
-}
-__host__ __device__ constexpr int wg_class_combo(int cl, int c1, int c2) { return (cl * OSC_CLASSES + c1) * OSC_CLASSES + c2; }
-__host__ __device__ constexpr int wg_kind_of(int base_kind, int cl, int c1, int c2) { return base_kind * kClassCombos + wg_class_combo(cl, c1, c2); }
-__host__ __device__ constexpr bool wg_base_kind_specialised(int base_kind) { (void)base_kind; return true; } // (== dsp_core.h welsh_base_kind_specialised; round 6: all six)
+// wave runs in a more demanding instantiation than its patch asks for.  WaveDesc, the kind numbering
+// (kBaseKinds, kClassCombos, kWgKinds, wg_base_kind_of, wg_class_combo, wg_kind_of): welsh_plan.h.
 template <int LFO_MODE, bool RETUNE> struct WavesBudget;
 template <> struct WavesBudget<LFO_F32, false> { static constexpr int value = GROOVE_WAVES_F32_STATIC; };
 template <> struct WavesBudget<LFO_F32, true> { static constexpr int value = GROOVE_WAVES_F32_RETUNE; };
@@ -826,8 +815,8 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_ANY) GROOVE_NO_TAIL_CALLS vo
 #endif // GROOVE_WELSH_ANY_TU
 // The four class-specialised base kinds in ONE kernel at the per-kind kernels' own register budget (all four are budgeted for five
 // waves per SIMD since round 5), the fp32-filter bodies included: the MIX kernel of big banks (round 6).  A block of a big bank is
-// THREE launches of it, one per kind stream, each over a third of the workgroup list taken with a stride of three (groove_hip.hip
-// welsh_upload_params: every launch carries the bank's own mix of kinds, most expensive first), instead of one launch per base kind:
+// THREE launches of it, one per kind stream, each over a third of the workgroup list taken with a stride of three (welsh_plan.h
+// welsh_plan: every launch carries the bank's own mix of kinds, most expensive first), instead of one launch per base kind:
 // with per-kind launches a stream's time per block is what ITS kinds cost — 460 / 455 / 222 us on the three streams for the 32-patch
 // benchmark table (profiles/r05_welsh-1m-window_summary.json), 462 / 546 / 266 for the library-proportioned one — and the slowest stream is
 // the step; thirds of everything are balanced whatever the patches are, and every stream has one launch per block (a launch cannot

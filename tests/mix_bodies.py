@@ -318,7 +318,7 @@ def state_words():
 
 
 def workgroups(params):
-    """The fused kernels' workgroups of a bank (groove_hip.hip welsh_upload_params, restated): virtual waves — runs of voices with the same
+    """The fused kernels' workgroups of a bank (csrc/welsh_plan.h welsh_plan, restated): virtual waves — runs of voices with the same
     patch, cut at 64 — ordered by (body key, WF_FILTER_F32) and cut into fours, a group's last workgroup filled up with empty waves that
     carry its first wave's patch.  Returns [(base kind, [(first voice, count, patch)] x 4)]; kinds 0 - 3 are the mix kernel's."""
     raw = [bytes(p) for p in params]
