@@ -590,8 +590,8 @@ GROOVE_HD double lp24_step(Lp24StateD& s, const Lp24CoefD& c, double x) {
 // The same two transposed-direct-form-II sections with fp32 coefficients and fp32 state: ten fp32 operations a frame instead of
 // ten f64 ones, no widening of the coefficients on a retuning frame (four conversions and four f64 operations), no conversion of
 // the input and the output.  Only for voices whose filter stays away from z = +1 AND z = -1 over its whole cutoff range
-// (WF_FILTER_F32: the host measures it when the bank is uploaded, derive.h welsh_filter_f32_ok), and only in the per-kind serial
-// kernels of big banks (kernels.h welsh_block<..., F32OK>): every other form keeps the f64 recurrence of DESIGN.md section 4.
+// (WF_FILTER_F32: the host measures it when the bank is uploaded, derive.h welsh_filter_f32_ok), and only in the fused mix
+// kernel of big banks (kernels.h welsh_block<..., F32OK>): every other form keeps the f64 recurrence of DESIGN.md section 4.
 // docs/DSP_SPEC.md "An fp32 filter kind" has the measurements that decided it.
 struct Lp24CoefF { float b0a, a1a, a2a, b0b, a1b, a2b; };
 struct Lp24StateF { float s0, s1, s2, s3; };

@@ -120,7 +120,7 @@ struct groove_bank {
   std::shared_ptr<LaneOrder> order; // device copy of plan.inv, shared with the blocks this bank's renders fill (groove_block: lazy lane order)
   uint8_t* d_wg_cls = nullptr;   // welsh: oscillator class pair of each entry of d_wg_list
   uint8_t* d_wg_base = nullptr;  // welsh: base kind of each entry of d_wg_list (the all-kinds kernel of small banks)
-  uint8_t* d_wg_f32 = nullptr;   // welsh: 1 where the entry's patches carry WF_FILTER_F32 (the fused per-kind kernels)
+  uint8_t* d_wg_f32 = nullptr;   // welsh: 1 where the entry's patches carry WF_FILTER_F32 (read by the fused mix kernel)
   // welsh: workgroup ids (groups of 4 virtual waves) sorted by kind (kernels.h).  All four d_wg_ arrays hold 2 * wg_list_cap entries: plan.sorted
   // from entry 0, plan.striped — the mix kernel's sections, [wg_list_cap + mix_off[s], + mix_cnt[s]) — from entry wg_list_cap
   uint32_t* d_wg_list = nullptr;
@@ -273,7 +273,7 @@ struct groove_ctx {
   // groove_mix_deferred takes the block's row-sum buffer AWAY from the block (owned_cap != 0: the pending rows live in a buffer
   // nobody else can write) and hands the block one of these instead; a consumed buffer comes back here (deferred_taken)
   std::vector<std::pair<float*, size_t>> spare_sums;
-  bool f32_filter = true; // WF_FILTER_F32: patches whose 24 dB filter is measured safe in fp32 take the fp32 recurrence in the per-kind kernels (GROOVE_F32_FILTER=0: never)
+  bool f32_filter = true; // WF_FILTER_F32: patches whose 24 dB filter is measured safe in fp32 take the fp32 recurrence in the fused mix kernel (GROOVE_F32_FILTER=0: never)
   std::vector<groove_bank*> paced_order; // banks with a pending paced reduction, in call order (= the order of their sums on a bus)
   float* d_fseg = nullptr;   // fused path: seg[segments][2*frames]
   size_t fseg_cap = 0;
@@ -1572,7 +1572,7 @@ enum class Form {
   TimeParallel,      // use_tp: one launch (welsh_tp.h), all three bank kinds
   WelshPerLane,      // n_vwaves == 0 (every voice its own patch): the per-lane kernel over the physical lanes
   WelshSmallUniform, // below the per-kind pipeline's threshold: all base kinds in one launch (launch_small_uniform)
-  WelshBigUniform,   // at or above it: the mix kernel and / or one kernel per base kind — several launches on several streams
+  WelshBigUniform,   // at or above it: the mix kernel's three sections and a kernel per exact-f64 kind (big_pieces), or one kernel per base kind (launch_render) — several launches on several streams
   FmSerial,          // one voice per lane
   SamplerSerial,
 };
@@ -1604,24 +1604,43 @@ static UniformArgs uniform_args(const groove_bank* b, float* out, float* rows, s
 #endif
   return a;
 }
-// The pieces of a wave-uniform bank: the per-base-kind slices of its kind-sorted workgroup list (welsh_plan.h KindSlices) ...
+// The per-base-kind slices of a wave-uniform bank's kind-sorted workgroup list (welsh_plan.h KindSlices).
 static KindSlices kind_slices(const groove_bank* b) { return kind_slices(b->plan.wgs_of_kind); }
-// One base kind's uniform Welsh kernel over `a`'s workgroups on stream `st`: every base kind has class-specialised bodies
-// (round 6: the two exact-f64 kinds too), one translation unit each (csrc/welsh_class.hip).
+// One base kind's own kernel over `a`'s workgroups on stream `st`, one translation unit each (csrc/welsh_class.hip).  Fused: the
+// exact-f64 kinds 4 and 5 only — the four others have no fused kernel of their own: the all-kinds, role-split and mix kernels carry them.
 static void launch_welsh_kind(int k, const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr) {
   typedef void (*Launcher)(const UniformArgs&, hipStream_t, bool, hipEvent_t);
   static constexpr Launcher of_kind[kBaseKinds] = {launch_welsh_uniform_specialised<0>, launch_welsh_uniform_specialised<1>, launch_welsh_uniform_specialised<2>,
                                                    launch_welsh_uniform_specialised<3>, launch_welsh_uniform_specialised<4>, launch_welsh_uniform_specialised<5>};
   of_kind[k](a, st, fused, done);
 }
-static void launch_kind_slice(const groove_bank* b, const KindSlices& p, int k, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
+// ... over the kind's slice of the bank's kind-sorted workgroup list
+static void launch_kind_slice(const groove_bank* b, int k, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
+  const KindSlices p = kind_slices(b);
   launch_welsh_kind(k, uniform_args(b, out, rows, p.offset[k], chs, frames, p.count[k]), st, fused, done);
 }
-// ... and the three sections of the MIX kernel (kernels.h; round 6): the class-specialised workgroups in three launches, each over a
-// third of them — the section's entries of the striped copies of all four lists (welsh_plan.h).
-static void launch_mix_section(const groove_bank* b, int sec, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
-  const size_t o = b->wg_list_cap + b->plan.mix_off[sec];
-  const UniformArgs a = uniform_args(b, out, rows, o, chs, frames, b->plan.mix_cnt[sec]);
+// The pieces of a BIG wave-uniform bank (Form::WelshBigUniform) in the pipelined fused and the asynchronous block-writing walks
+// (the synchronous one has its own: launch_render), in launch order, longest walk first: the exact-f64 kinds 5 and 4, a
+// kernel each over the kind's slice of the sorted list, then sections 2, 1, 0 of the MIX kernel (kernels.h; round 6) — the
+// class-specialised workgroups in three launches, each over a third of them: the section's entries of the striped copies of all four
+// lists (welsh_plan.h).  A piece is named by the side stream the pipelined and asynchronous walks give it: kind k -> k, section s -> s.
+// Empty pieces are left out.
+struct BigPieces {
+  int k[5]; int n = 0;
+  const int* begin() const { return k; }
+  const int* end() const { return k + n; }
+};
+static BigPieces big_pieces(const groove_bank* b) {
+  BigPieces l;
+  const KindSlices p = kind_slices(b);
+  for (int k = kBaseKinds - 1; k >= 4; --k) if (p.count[k]) l.k[l.n++] = k;
+  for (int sec = 2; sec >= 0; --sec) if (b->plan.mix_cnt[sec]) l.k[l.n++] = sec;
+  return l;
+}
+static void launch_piece(const groove_bank* b, int piece, bool fused, size_t chs, float* out, float* rows, uint32_t frames, hipStream_t st, hipEvent_t done = nullptr) {
+  if (piece >= 4) { launch_kind_slice(b, piece, fused, chs, out, rows, frames, st, done); return; }
+  const size_t o = b->wg_list_cap + b->plan.mix_off[piece];
+  const UniformArgs a = uniform_args(b, out, rows, o, chs, frames, b->plan.mix_cnt[piece]);
   if (fused) launch_welsh_uniform_mix(a, b->d_wg_base + o, st, done);
   else launch_welsh_uniform_mix_unfused(a, b->d_wg_base + o, st, done);
 }
@@ -1683,7 +1702,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
       else launch_bound(sampler_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
       break;
-    case Form::WelshBigUniform: break; // (the callers' own walks over kind_slices / launch_mix_section: their stream policies differ on purpose)
+    case Form::WelshBigUniform: break; // (the callers' own walks over big_pieces / the base kinds: their stream policies differ on purpose)
   }
 }
 // groove_bank_render and the non-pipelined groove_bank_render_mix: everything on the ctx stream, but for the big uniform form.
@@ -1692,31 +1711,28 @@ static int launch_render(groove_bank* b, uint32_t frames, bool fused, size_t chs
   b->ctx_touched = true;
   const Form form = form_of(b, frames);
   if (form == Form::WelshBigUniform) {
-    // One kernel per base kind present, all running concurrently: the most expensive kind goes
-    // out first on the ctx stream (list scheduling, longest first), the others on side streams
-    // forked from it, and the ctx stream joins them before the bus reduction.
+    // One block-writing kernel per base kind present, all running concurrently: the most expensive kind goes out first on the ctx
+    // stream (list scheduling, longest first), the others on side streams forked from it, and the ctx stream joins them before
+    // whatever reads the block.  (Not big_pieces: at 1,000,000 voices the mix kernel's three launches take 0.912 ms per block here
+    // where these take 0.857 — docs/HISTORY.md section 17; the bits are the same.)
+    if (fused) return fail(ctx, "launch_render: the fused render of a big uniform bank is render_mix_pipelined's"); // (groove_bank_render_mix sends it there)
     const KindSlices p = kind_slices(b);
     int present = 0;
     for (uint32_t c : p.count) present += c ? 1 : 0;
     if (present > 1) GHIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    int side = 0;
-    bool first_kind = true;
+    int side = -1; // the first kind: the ctx stream
     for (int k = kBaseKinds - 1; k >= 0; --k) {
       if (!p.count[k]) continue;
-      hipStream_t st = ctx->stream;
-      if (!first_kind) {
-        st = side_stream_of(ctx, side);
-        GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0));
-      }
-      launch_kind_slice(b, p, k, fused, chs, out, rows, frames, st);
-      if (!first_kind) {
+      hipStream_t st = side < 0 ? ctx->stream : side_stream_of(ctx, side);
+      if (side >= 0) GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0));
+      launch_kind_slice(b, k, false, chs, out, rows, frames, st);
+      if (side >= 0) {
         GHIP(ctx, hipEventRecord(ctx->ev_join[side], st));
         GHIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[side], 0));
-        ++side;
       }
-      first_kind = false;
-      ctx->need_fork = true; // ctx-stream work the pipelined path's side streams must see
+      ++side;
     }
+    ctx->need_fork = true; // ctx-stream work the pipelined path's side streams must see
   } else {
     launch_single(b, form, frames, fused, chs, out, rows, ctx->stream);
   }
@@ -1815,19 +1831,11 @@ static int render_async_impl(groove_bank* b, uint32_t frames, groove_block* out,
     ctx->side_busy[k] = true;
   };
   if (uniform) {
-    const KindSlices p = kind_slices(b);
-    // the exact-f64 kinds keep their per-kind kernels, most expensive first; the other four take the MIX kernel (block-writing form: kernels.h)
-    for (int k = kBaseKinds - 1; k >= 4; --k) {
-      if (!p.count[k]) continue;
+    // the exact-f64 kinds' own kernels and the MIX kernel's sections in its block-writing form, each on its own side stream
+    for (int k : big_pieces(b)) {
       hipStream_t st = begin(k);
-      launch_kind_slice(b, p, k, false, chs, dst, rows, frames, st);
+      launch_piece(b, k, false, chs, dst, rows, frames, st);
       end(k);
-    }
-    for (int sec = 2; sec >= 0; --sec) {
-      if (!b->plan.mix_cnt[sec]) continue;
-      hipStream_t st = begin(sec);
-      launch_mix_section(b, sec, false, chs, dst, rows, frames, st);
-      end(sec);
     }
   } else {
     const int k = b->stream_slot;
@@ -1917,18 +1925,11 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
     GHIP(ctx, hipEventCreateWithFlags(&b->ev_reduce_done[slot], kSyncEventFlags));
     for (int k = 0; k < kSideStreams; ++k) GHIP(ctx, hipEventCreateWithFlags(&b->ev_render_done[k][slot], kSyncEventFlags));
   }
-  // Which side streams carry a launch.  The MIX kernel (kernels.h; round 6): the four class-specialised base kinds in three launches,
-  // one per kind stream, each over a third of their workgroups (every third entry of the kind-sorted list); the exact-f64 kinds
-  // keep their per-kind kernels.
-  KindSlices p;
-  uint32_t launches = 0;
-  if (uniform) {
-    p = kind_slices(b);
-    for (int sec = 0; sec < 3; ++sec) if (b->plan.mix_cnt[sec]) launches |= 1u << sec; // streams 0 - 2: the mix launches; 4, 5: the exact-f64 kinds; 3: nothing
-    for (int k = 4; k < kBaseKinds; ++k) if (p.count[k]) launches |= 1u << k;
-  } else if (rows) {
-    launches = 1u << b->stream_slot; // one kernel, on this bank's side stream (the loop below runs once)
-  }
+  // Which side streams carry a launch, in launch order: a big uniform bank's pieces (big_pieces: streams 5, 4 the exact-f64 kinds, 2 - 0
+  // the mix launches, 3 nothing); every other form is one kernel on the bank's own side stream.
+  int on[kSideStreams], n_on = 0;
+  if (uniform) for (int piece : big_pieces(b)) on[n_on++] = piece; // (a piece's name IS its side stream)
+  else if (rows) on[n_on++] = b->stream_slot;
   if (ctx->need_fork) { // side streams must see what the ctx stream did since the last join (note events, uploads)
     GHIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     for (bool& f : ctx->fork_pending) f = true;
@@ -1947,8 +1948,8 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
     else GHIP(ctx, e);
   }
   uint32_t used = 0;
-  for (int k = kSideStreams - 1; k >= 0; --k) { // most expensive Welsh kind first
-    if (!(launches & (1u << k))) continue;
+  for (int i = 0; i < n_on; ++i) {
+    const int k = on[i];
     hipStream_t st = side_stream_of(ctx, k);
     used |= 1u << k;
     if (ctx->fork_pending[k]) { GHIP(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0)); ctx->fork_pending[k] = false; }
@@ -1957,8 +1958,7 @@ static int render_mix_pipelined(groove_bank* b, uint32_t frames, float* bus_dev,
     // this block's kernel and the next block's on the stream
     const hipEvent_t done = ctx->bind_events ? b->ev_render_done[k][slot] : nullptr;
     float* part = b->d_pipe_part[slot];
-    if (uniform && k < 3) launch_mix_section(b, k, true, 0, part, part, frames, st, done);
-    else if (uniform) launch_kind_slice(b, p, k, true, 0, part, part, frames, st, done);
+    if (uniform) launch_piece(b, k, true, 0, part, part, frames, st, done);
     else launch_single(b, form, frames, true, 0, part, part, st, done);
     if (!done) GHIP(ctx, hipEventRecord(b->ev_render_done[k][slot], st));
     if (!paced) GHIP(ctx, hipStreamWaitEvent(ctx->stream, b->ev_render_done[k][slot], 0));

@@ -48,22 +48,10 @@ __device__ __forceinline__ void soa_store(uint32_t* __restrict__ buf, uint32_t n
     __builtin_amdgcn_raw_buffer_store_b32((int)t.w[i], rsrc, (int)(v * 4u), (int)(i * n * 4u), 0);
 }
 
-// Waves per SIMD each uniform-kernel kind is register-budgeted for (512 VGPRs / waves, in steps of 8).  Re-measured on
-// the un-packed code (-fno-slp-vectorize), 1,000,000 voices, in-job: F32 kinds 5 -> +1.8 % in the all-voices window
-// (+-0 over the project), 4 the same, 8 -> -12 %; smooth kinds 6 -> -3 %, 3 -> -10 %.
-#ifndef GROOVE_WAVES_F32_STATIC
-#define GROOVE_WAVES_F32_STATIC 5
-#endif
-#ifndef GROOVE_WAVES_F32_RETUNE
-#define GROOVE_WAVES_F32_RETUNE 5
-#endif
-#ifndef GROOVE_WAVES_SMOOTH_STATIC
-#define GROOVE_WAVES_SMOOTH_STATIC 5 /* round 5: 5 (102 VGPRs) instead of 4 for both smooth-f64 kinds — after the polynomial envelopes and the in-place phase
-                                        add their bodies fit: the driver's window 0.4395 -> 0.4329 ms per block (median of five, in-job, profiles/r05_budgets_ab.log);
-                                        the fp32-LFO kinds at 6 lose (0.4555 against 0.4439) */
-#endif
-#ifndef GROOVE_WAVES_SMOOTH_RETUNE
-#define GROOVE_WAVES_SMOOTH_RETUNE 5
+// Waves per SIMD a kernel is register-budgeted for (512 VGPRs / waves, in steps of 8).  The four class-specialised base kinds have ONE
+// budget, the mix kernel's and their own block-writing kernels' (how five was measured for each of them: docs/HISTORY.md section 17).
+#ifndef GROOVE_WAVES_MIX
+#define GROOVE_WAVES_MIX 5
 #endif
 #ifndef GROOVE_WAVES_F64
 #define GROOVE_WAVES_F64 4 /* round 6: 4 (128 VGPRs) instead of 2, with class-specialised bodies for these kinds too.  Not for their own occupancy — they
@@ -592,13 +580,17 @@ __global__ __launch_bounds__(kThreads) void welsh_render_kernel(
 // workgroup runs in:
 //   - the LFO mode (dsp_core.h: none in f64 / smooth recurrences / exact f64) and whether the
 //     filter is retuned per frame (envelope- or LFO-driven cutoff: per-lane f64 coefficients, the
-//     tan / reciprocal path) or static (coefficients in SGPRs): six BASE KINDS, one kernel each,
-//     launched concurrently on forked streams over their slices of a kind-sorted workgroup list.
-//     Separate kernels because register allocation is per kernel: the cheapest base kind fits 72
-//     VGPRs (7 waves / SIMD), the most expensive needs 133 (3 waves); inside one kernel everybody
-//     paid for the maximum.
+//     tan / reciprocal path) or static (coefficients in SGPRs): six BASE KINDS over a kind-sorted
+//     workgroup list.  The two exact-f64 kinds (4, 5) have a kernel each, welsh_render_uniform_kernel,
+//     because register allocation is per kernel and their bodies need 133 VGPRs; the four others fit
+//     one budget of five waves per SIMD since round 5 and share a kernel — the all-kinds kernel of
+//     small banks, the role-split kernel (welsh_split.h), the mix kernel of big banks — that reads the
+//     base kind per workgroup (wg_base[]).  Their own kernels (one per base kind, launched concurrently
+//     on forked streams: every big bank's form until round 6) remain in the block-writing form alone,
+//     for the synchronous groove_bank_render of a big bank, where they are faster than the mix kernel's
+//     three launches (docs/HISTORY.md section 17).
 //   - the CLASSES of the LFO and the two audio oscillators (dsp_core.h, "Oscillator CLASSES"): inside
-//     every base kind's kernel (fused and materialised form; the two exact-f64 kinds since round 6), one
+//     every one of these kernels (fused and block-writing form), one
 //     scalar switch per workgroup calls the copy of the whole block body compiled for its class triple
 //     (6 x 5 x 5 copies; 3 x 5 x 5 for the smooth-LFO kinds).  The copies are NOT inlined:
 //     each is a function with its own register allocation (inlined, their hoisted loop invariants
@@ -610,18 +602,11 @@ __global__ __launch_bounds__(kThreads) void welsh_render_kernel(
 // descriptors are ordered by kind, a kind's last workgroup is filled up with empty waves), so no
 // wave runs in a more demanding instantiation than its patch asks for.  WaveDesc, the kind numbering
 // (kBaseKinds, kClassCombos, kWgKinds, wg_base_kind_of, wg_class_combo, wg_kind_of): welsh_plan.h.
-template <int LFO_MODE, bool RETUNE> struct WavesBudget;
-template <> struct WavesBudget<LFO_F32, false> { static constexpr int value = GROOVE_WAVES_F32_STATIC; };
-template <> struct WavesBudget<LFO_F32, true> { static constexpr int value = GROOVE_WAVES_F32_RETUNE; };
-template <> struct WavesBudget<LFO_F64_SMOOTH, false> { static constexpr int value = GROOVE_WAVES_SMOOTH_STATIC; };
-template <> struct WavesBudget<LFO_F64_SMOOTH, true> { static constexpr int value = GROOVE_WAVES_SMOOTH_RETUNE; };
-template <> struct WavesBudget<LFO_F64, false> { static constexpr int value = GROOVE_WAVES_F64; };
-template <> struct WavesBudget<LFO_F64, true> { static constexpr int value = GROOVE_WAVES_F64; };
 // The one kernel argument (so that the non-inlined bodies can read it from the kernarg segment
 // with scalar loads instead of taking a dozen uniform values through VGPR arguments).
 struct UniformArgs {
   const WaveDesc* waves; uint32_t* state; float* out; float* rows; const uint32_t* wg_list; const uint8_t* wg_cls;
-  const uint8_t* wg_f32; // per workgroup of the list: its patches carry WF_FILTER_F32 (read by the fused per-kind kernels only)
+  const uint8_t* wg_f32; // per workgroup of the list: its patches carry WF_FILTER_F32 (read by the fused mix kernel only)
   size_t ch_stride; RenderConsts rc; uint32_t n_waves, n, frames, n_wgs; // out: the planar block (block-writing form); rows: partial[workgroup][ch][frame] (both forms)
   TpPrev prev; // groove_bank_render_mix_deferred: the previous block's rows, to be put on their bus by this launch (the all-kinds and role-split kernels)
   uint32_t* diag = nullptr; // the context's DiagCounters (diag.h)
@@ -743,12 +728,12 @@ __device__ __forceinline__ void welsh_dispatch_class(uint32_t cls, UniformArgsPt
 #undef GROOVE_CLS_ROW
 #undef GROOVE_CLS_CASE
 }
-// SPECIALISED = false: the whole launch runs the OSC_ANY x OSC_ANY body (wg_cls is not read).
+// The kernel of ONE base kind, class-specialised bodies, f64 filter: the exact-f64 kinds 4 and 5 in both forms, kinds 0 - 3 in the
+// block-writing form only (their fused work is the all-kinds, role-split and mix kernels').  (The parameter list is kept for the
+// names that committed profiles show — docs/HISTORY.md section 16.)
 template <bool FUSED, int LFO_MODE, bool RETUNE, bool SPECIALISED>
-__global__ __launch_bounds__(kThreads, (WavesBudget<LFO_MODE, RETUNE>::value)) GROOVE_NO_TAIL_CALLS void welsh_render_uniform_kernel(UniformArgs a) {
-  // (No s_setprio for the class-specialised kinds: raising the f64-LFO kinds' wave priority paid when a block's kernels were forked and
-  // joined; with the blocks pipelined the longest kernel is the most numerous kind, and any priority
-  // costs 5 % — measured: none 0.460 ms, f64-LFO kinds raised 0.484, F32-retune raised 0.513.)
+__global__ __launch_bounds__(kThreads, (LFO_MODE == LFO_F64 ? GROOVE_WAVES_F64 : GROOVE_WAVES_MIX)) GROOVE_NO_TAIL_CALLS void welsh_render_uniform_kernel(UniformArgs a) {
+  static_assert(SPECIALISED && (LFO_MODE == LFO_F64 || !FUSED), "no fused kernel of base kinds 0 - 3: the all-kinds, role-split and mix kernels run them");
   const UniformArgsPtr ka = (UniformArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(); // == &a, in the constant address space
   // (Round 6, the exact-f64 kinds beside the mix kernel's three launches: their few wavefronts — 1.9 % of a library-proportioned bank's
   // voices — take the block's longest walk, ~410 us beside mix launches of ~350, 227 us alone.  s_setprio(3) for these kernels changed
@@ -762,19 +747,8 @@ __global__ __launch_bounds__(kThreads, (WavesBudget<LFO_MODE, RETUNE>::value)) G
 #define GROOVE_HB_DONE do { } while (0)
 #endif
   if constexpr (FUSED) { if (welsh_idle_workgroup(a)) { GROOVE_HB_DONE; return; } }
-  if constexpr (!SPECIALISED) {
-    welsh_uniform_body_impl<FUSED, LFO_MODE, RETUNE, OSC_ANY, OSC_ANY, OSC_ANY>(ka);
-  } else {
-    // The FUSED per-kind kernels honour WF_FILTER_F32 (a second set of block bodies); the block-writing per-kind kernels and the
-    // all-kinds, role-split and time-parallel kernels keep the f64 filter for every voice.
-    const uint32_t cls = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.wg_cls[GROOVE_WG_SLOT(a.n_wgs)]);
-    if constexpr (FUSED && LFO_MODE != LFO_F64) {
-      if (__builtin_amdgcn_readfirstlane((int)a.wg_f32[GROOVE_WG_SLOT(a.n_wgs)])) welsh_dispatch_class<FUSED, LFO_MODE, RETUNE, true>(cls, ka);
-      else welsh_dispatch_class<FUSED, LFO_MODE, RETUNE, false>(cls, ka);
-    } else {
-      welsh_dispatch_class<FUSED, LFO_MODE, RETUNE, false>(cls, ka);
-    }
-  }
+  const uint32_t cls = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.wg_cls[GROOVE_WG_SLOT(a.n_wgs)]);
+  welsh_dispatch_class<FUSED, LFO_MODE, RETUNE, false>(cls, ka);
   GROOVE_HB_DONE;
 #undef GROOVE_HB_DONE
 }
@@ -813,8 +787,8 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_ANY) GROOVE_NO_TAIL_CALLS vo
 #undef GROOVE_ANY_CASE
 }
 #endif // GROOVE_WELSH_ANY_TU
-// The four class-specialised base kinds in ONE kernel at the per-kind kernels' own register budget (all four are budgeted for five
-// waves per SIMD since round 5), the fp32-filter bodies included: the MIX kernel of big banks (round 6).  A block of a big bank is
+// The four class-specialised base kinds in ONE kernel at the register budget their per-kind kernels had (five waves per SIMD each
+// since round 5), the fp32-filter bodies included: the MIX kernel of big banks (round 6).  A block of a big bank is
 // THREE launches of it, one per kind stream, each over a third of the workgroup list taken with a stride of three (welsh_plan.h
 // welsh_plan: every launch carries the bank's own mix of kinds, most expensive first), instead of one launch per base kind:
 // with per-kind launches a stream's time per block is what ITS kinds cost — 460 / 455 / 222 us on the three streams for the 32-patch
@@ -830,9 +804,6 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_ANY) GROOVE_NO_TAIL_CALLS vo
 // docs/HISTORY.md): 57 - 110 instructions a frame where the shared loop's table path ran 130 - 170.  In one job, headline
 // 0.3301 - 0.3331 -> 0.3118 - 0.3172 ms per block, the library-proportioned bank 0.3376 -> 0.3293, the whole timeline 0.2751 -> 0.2628.  The
 // promise is a counted assertion (diag.h fast_table_misses, required to be 0 like zero_segments).
-#ifndef GROOVE_WAVES_MIX
-#define GROOVE_WAVES_MIX 5
-#endif
 #ifdef GROOVE_WELSH_MIX_TU // defined by the translation units that own this kernel (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=10 fused, 11 block-writing)
 template <bool FUSED>
 __global__ __launch_bounds__(kThreads, GROOVE_WAVES_MIX) GROOVE_NO_TAIL_CALLS void welsh_render_uniform_mix_kernel(UniformArgs a, const uint8_t* __restrict__ wg_base) {
@@ -866,8 +837,8 @@ __global__ __launch_bounds__(kThreads, GROOVE_WAVES_MIX) GROOVE_NO_TAIL_CALLS vo
 }
 #endif // GROOVE_WELSH_MIX_TU
 static_assert(OSC_CLASSES == 5 && LFO_CLASSES == 6 && kClassCombos <= 256, "the class switch above lists 6 x 5 x 5 combinations, one byte each");
-// Launchers of the class-specialised per-kind kernels, one translation unit each
-// (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5) so that they compile in parallel.
+// Launchers of the wave-uniform kernels, one translation unit each (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5, 8 - 11) so that
+// they compile in parallel.
 // `done` (optional, every launcher below): an event that completes WITH the kernel — bound to the dispatch's own completion signal
 // (hipExtLaunchKernelGGL) instead of recorded behind it: a recorded event is a barrier packet of its own, ~5 us of its stream's timeline
 // before the next kernel of the stream starts.
@@ -876,7 +847,7 @@ static inline void launch_bound(K kernel, dim3 grid, dim3 blk, hipStream_t st, h
   if (done) hipExtLaunchKernelGGL(kernel, grid, blk, 0, st, nullptr, done, 0, args...);
   else hipLaunchKernelGGL(kernel, grid, blk, 0, st, args...);
 }
-template <int BASE_KIND> // defined and instantiated by the base kind's translation unit (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5; 4, 5: the exact-f64 LFO kinds)
+template <int BASE_KIND> // defined and instantiated by the base kind's translation unit (csrc/welsh_class.hip, -DGROOVE_BASE_KIND=0..5); `fused`: the exact-f64 LFO kinds 4 and 5 only
 void launch_welsh_uniform_specialised(const UniformArgs& a, hipStream_t st, bool fused, hipEvent_t done);
 void launch_welsh_uniform_any(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done = nullptr); // fused: csrc/welsh_class.hip, -DGROOVE_BASE_KIND=9
 void launch_welsh_uniform_any_unfused(const UniformArgs& a, const uint8_t* wg_base, hipStream_t st, hipEvent_t done = nullptr); // writes the voice block: -DGROOVE_BASE_KIND=8

@@ -94,9 +94,9 @@ uint32_t groove_time_parallel_max_voices(groove_ctx* ctx);
 int groove_set_time_parallel_pair_min_voices(groove_ctx* ctx, uint32_t min_voices);
 uint32_t groove_time_parallel_pair_min_voices(groove_ctx* ctx);
 /* Tuning: Welsh banks of at least this many (virtual) wavefronts — 64 voices each; default 3,800 = ~243,000 voices — run
- * one kernel per base kind and pipeline consecutive fused blocks; smaller ones take one launch for all kinds.  1 forces
- * the per-kind pipelined form for every size (tests and bench.py's parity sample use it to run the kernels of the
- * million-voice path on a small bank).  GROOVE_PIPELINE_MIN_WAVES in the environment sets it at groove_init. */
+ * the mix kernel (three launches over thirds of the workgroups, and one kernel per exact-f64 base kind) and pipeline
+ * consecutive fused blocks; smaller ones take one launch for all kinds.  1 forces that big-bank form for every size (tests
+ * and bench.py's parity sample use it to run the kernels of the million-voice path on a small bank).  GROOVE_PIPELINE_MIN_WAVES in the environment sets it at groove_init. */
 int groove_set_pipeline_min_waves(groove_ctx* ctx, uint32_t waves);
 uint32_t groove_pipeline_min_waves(groove_ctx* ctx);
 /* Which look-aheads the wave-uniform Welsh kernels may use (csrc/kernels.h): bit 0 — a wave whose live voices share the filter
@@ -208,7 +208,7 @@ int groove_block_release(groove_block* b);
  * accumulate = 0 overwrites the bus, 1 adds to it.
  * Asynchronous like every call here: the bus is complete for anything ordered after this call on the
  * ctx stream (groove_download, groove_bus_to_i16, groove_bus_reduce, groove_synchronize ...).  Large
- * Welsh banks pipeline consecutive calls (block b+1's voice kernels, on the library's own per-kind
+ * Welsh banks pipeline consecutive calls (block b+1's voice kernels, on the library's own side
  * streams, do not wait for block b's bus sum); calls that touch the bank in between (note events,
  * groove_bank_set_param, groove_bank_render, groove_bank_download_state) join that pipeline first, so
  * the order of effects is the order of calls.  The voices' lane order inside the library is its own

@@ -3,7 +3,7 @@
 
 A BODY KEY is (base kind, LFO class, oscillator-1 class, oscillator-2 class, fp32-filter flag), read from the library's own rule
 (dsp_core.h welsh_base_kind / welsh_body_classes, derive.h welsh_filter_f32_ok) through tests/emul (emul_welsh_classify).  The flag
-names the fp32-filter copy of a body, which only the fused kernels of kinds 0 - 3 carry; the exact-f64 kinds 4 and 5 ignore it
+names the fp32-filter copy of a body, which only the fused mix kernel carries (kinds 0 - 3); the exact-f64 kinds 4 and 5 ignore it
 (kernels.h welsh_render_uniform_kernel), so their keys carry 0.
 
 The classifier reads the two oscillators' waveforms for the oscillator classes and nothing else of them; it reads the LFO (waveform,
@@ -231,21 +231,25 @@ def bounded(p, voices=None):
 _REPS = None
 
 
+def representative(k):
+    """The representative of key k: its first grid point that is classified as k, bounded and sounding in the oracle over the timeline
+    (None: the key has none)."""
+    if _REPS is not None:
+        return _REPS.get(k)
+    for p in _candidates(k):
+        if key(p) == k and bounded(p):
+            return p
+    return None
+
+
 def representatives():
-    """{key: patch}: one representative per reachable key, classified as that key, bounded and sounding in the oracle over the timeline."""
+    """{key: patch}: representative(k) of every reachable key."""
     global _REPS
     if _REPS is None:
         keys = sorted(reachable_keys())
-
-        def pick(k):
-            for p in _candidates(k):
-                if key(p) == k and bounded(p):
-                    return k, p
-            return k, None
-
         _lib()
         with ThreadPoolExecutor(16) as pool:
-            _REPS = dict(pool.map(pick, keys))
+            _REPS = dict(zip(keys, pool.map(representative, keys)))
     return _REPS
 
 

@@ -274,7 +274,7 @@ def test_a_torn_record_is_the_only_way_to_a_zero_frame_segment():
 def test_fp32_filter_kind_stays_within_the_bars(oracle):
     """The arithmetic policy TESTED: patches whose 24 dB filter the host measures safe in fp32
     (derive.h welsh_filter_f32_ok -> WF_FILTER_F32: the two recurrences side by side at the lowest, middle and highest cutoff the
-    patch can reach, <= 2e-6) run the fp32 recurrence in the fused per-kind kernels of big banks (dsp_core.h welsh_frame<..., F32FILT>,
+    patch can reach, <= 2e-6) run the fp32 recurrence in the fused mix kernel of big banks (dsp_core.h welsh_frame<..., F32FILT>,
     mirrored here frame for frame).  Over the whole 172-block timeline of the 32 benchmark patches: 19 qualify — none of those
     whose filter comes near z = +1 (40 - 90 Hz) or z = -1 (sweeps up to 20 kHz) — every flagged voice stays within 2e-6 RMS of the
     f64 oracle, no voice is worse than the f64 form's worst, and the bus moves by 1e-8."""

@@ -1,11 +1,11 @@
-"""GPU tier: the fp32 filter kind (docs/DSP_SPEC.md section 11).  The FUSED per-kind kernels of big banks run the 24 dB filter of
+"""GPU tier: the fp32 filter kind (docs/DSP_SPEC.md section 11).  The FUSED mix kernel of big banks runs the 24 dB filter of
 patches the host has measured safe (WF_FILTER_F32) in fp32, through a second set of block bodies; every other kernel form keeps the
 f64 recurrence.  Checked here on the 32 benchmark patches, one patch per workgroup (256 identical voices: the bank's bus / 256 is one
 voice per patch), whole 172-block timeline with its note-off:
-  * per-kind kernels (forced by the ABI's tuning knob) against the oracle, patch by patch: flagged patches <= 2e-6 RMS, all <= 1e-5;
+  * the big-bank form ("per-kind" below: the mix kernel, forced by the ABI's tuning knob) against the oracle, patch by patch: flagged patches <= 2e-6 RMS, all <= 1e-5;
   * against the all-kinds kernel (f64 filter for everybody): unflagged patches bit for bit, flagged patches not — they did take
     the other recurrence — and exactly the 19 patches the emulation tier's criterion names;
-  * GROOVE_F32_FILTER=0 in a fresh process: the per-kind kernels' bus is the all-kinds kernel's, bit for bit, for all 32;
+  * GROOVE_F32_FILTER=0 in a fresh process: the mix kernel's bus is the all-kinds kernel's, bit for bit, for all 32;
   * a voice can change kernel form between blocks (the fp32 state lives in the record's f64 fields): per-kind for 40 blocks, then
     time-parallel, stays within the bar."""
 import ctypes as C

@@ -166,7 +166,7 @@ def test_library_workload_full_size(gpu_ctx, oracle):
 def test_coefficient_look_ahead_is_the_per_lane_retune_bit_for_bit(gpu_ctx, oracle):
     """kernels.h "coefficient look-ahead": a wave whose live voices share the filter envelope's stage takes its filter coefficients from a
     table that lane j filled for frame k + j; a wave whose voices started apart retunes lane by lane.  The same voices through both: 256
-    voices of ONE envelope-retuned patch in the per-kind (mix) kernels, (A) all struck in block 0 — every wave uniform — and (B) the odd
+    voices of ONE envelope-retuned patch in the per-kind (block-writing) and mix (fused) kernels, (A) all struck in block 0 — every wave uniform — and (B) the odd
     voices struck a block later — every wave mixed.  The even voices, whose own history is the same in A and B, must come out the same
     BITS (a voice's samples do not depend on its neighbours), and both runs must match the oracle; for an f64-filter patch and for one
     the host lets filter in fp32.

@@ -98,7 +98,7 @@ def _flagged(params):
 def test_random_patches_every_kernel_form_against_the_oracle(gpu_ctx, oracle):
     """Patches DRAWN from a seed (groove_amd.patches.random_welsh_patch: every continuous parameter, every routing, instant attacks, zero
     sustains, cutoffs from 40 Hz to 20 kHz) instead of the 32 benchmark ones, eight per bank in runs of eight voices on random keys, 40 blocks
-    with a note-off: every kernel form — time-parallel, the all-kinds serial kernel, role-split, the per-kind kernels with their fp32 filter
+    with a note-off: every kernel form — time-parallel, the all-kinds serial kernel, role-split, the mix kernel with its fp32 filter
     bodies — against the f64 oracle voice by voice (<= 1e-5 RMS of the larger of full scale and the voice's level; measured worst of 60 x 64 voices: 2.1e-6), role-split bit for bit the
     serial kernel's.  No key is an A: 55 and 110 Hz are rational in 44,100 and put a square's edge EXACTLY on a frame, which the oracle's
     accumulated f64 phase and the device's 64-bit counter decide differently (docs/DSP_SPEC.md section 2)."""
