@@ -23,7 +23,10 @@ FX_GAIN, FX_BITCRUSHER, FX_BIQUAD_LP12, FX_BIQUAD_LP24, FX_CHORUS, FX_DELAY, FX_
 CTL_FX_CEILING, CTL_FX_BITS, CTL_FX_CUTOFF, CTL_FX_Q, CTL_FX_PASSBAND_RIPPLE, CTL_FX_ATTENUATION, CTL_FX_WET, CTL_FX_THRESHOLD = range(8)
 CTL_WELSH_DCA_GAIN, CTL_WELSH_DCA_PAN, CTL_WELSH_CUTOFF = 32, 33, 34
 # groove_ctl_source_kind, groove_ctl_law
-CTL_SRC_LFO, CTL_SRC_SIGNAL = range(2)
+CTL_SRC_LFO, CTL_SRC_SIGNAL, CTL_SRC_TRIP = range(3)
+# groove_ctl_step_kind, GROOVE_CTL_UNITS_PER_BEAT
+CTL_STEP_FLAT, CTL_STEP_SLOPE, CTL_STEP_LOGARITHMIC, CTL_STEP_EXPONENTIAL = range(4)
+CTL_UNITS_PER_BEAT = 65536
 CTL_LAW_BIPOLAR, CTL_LAW_AMPLITUDE, CTL_LAW_AMPLITUDE_INVERTED = range(3)
 
 
@@ -90,6 +93,22 @@ def ctl_sources(n, **kw):
         for k, v in kw.items():
             setattr(s, k, v)
     return arr
+
+
+class CtlStep(C.Structure):
+    """groove_ctl_step: one step of a control trip."""
+    _fields_ = [("kind", C.c_uint32), ("start", C.c_double), ("end", C.c_double), ("beats", C.c_double)]
+
+
+def ctl_steps(lanes):
+    """[[(kind, start, end, beats), ...] per source lane] (equal step counts) -> (ctypes array [n_src][n_steps], n_steps)."""
+    n_steps = len(lanes[0])
+    assert all(len(lane) == n_steps for lane in lanes)
+    arr = (CtlStep * (len(lanes) * max(n_steps, 1)))()
+    for s, lane in enumerate(lanes):
+        for i, (kind, start, end, beats) in enumerate(lane):
+            arr[s * n_steps + i] = CtlStep(kind, start, end, beats)
+    return arr, n_steps
 
 
 def fx_params(**kw):

@@ -50,6 +50,53 @@ GROOVE_HD float ctl_signal_value01(uint32_t law, float m) {
   }
 }
 
+// ------------------------------------------------------------------ trip source
+// A CONTROL TRIP (the host layer's ControlTrip): start_beat plus S steps {kind, start, end, beats}.  begin[0] = start_beat and
+// begin[i + 1] = begin[i] + beats[i], accumulated in f64 in the order ControlTrip::work accumulates its `b` (ctl_trip_begins: the one
+// place that does it); step i holds `now` iff begin[i] <= now < begin[i + 1].  The begins never decrease, so at most one step holds a
+// given `now` and a binary search finds the step the host's first-match scan finds.
+GROOVE_HD double ctl_trip_now(uint64_t at_units) { return (double)at_units / (double)GROOVE_CTL_UNITS_PER_BEAT; }
+// begin[0 .. n_steps] from the beats of one source lane, `stride` elements apart in both arrays
+GROOVE_HD void ctl_trip_begins(double start_beat, const double* beats, size_t beats_stride, uint32_t n_steps, double* begin, size_t stride) {
+  double b = start_beat;
+  begin[0] = b;
+  for (uint32_t i = 0; i < n_steps; ++i) {
+    b += beats[(size_t)i * beats_stride];
+    begin[(size_t)(i + 1) * stride] = b;
+  }
+}
+// The step that holds `now` among begin[0 .. n_steps] (stride elements apart: the device table is [step][lane]), or -1 outside
+// [begin[0], begin[n_steps]).
+GROOVE_HD int32_t ctl_trip_find(const double* begin, size_t stride, uint32_t n_steps, double now) {
+  if (!(now >= begin[0]) || !(now < begin[(size_t)n_steps * stride])) return -1;
+  uint32_t lo = 0, hi = n_steps; // begin[lo] <= now < begin[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (now >= begin[(size_t)mid * stride]) lo = mid; else hi = mid;
+  }
+  return (int32_t)lo;
+}
+GROOVE_HD bool ctl_trip_kind_ok(uint32_t kind) { return kind <= GROOVE_CTL_STEP_EXPONENTIAL; }
+// ControlTrip::value_at in f64: t = (now - begin) / beats clamped to 0..1; flat, slope, and the two MMA curves (convex / concave
+// transforms of the linear ramp) with their threshold 10^(-12/5) as the double pow(10, -12 / 5) gives.  Every product and sum is
+// rounded by itself: device code is built with contraction on, and a fused start + (end - start) * t would not give the host's bits.
+GROOVE_HD double ctl_trip_value(uint32_t kind, double start, double end, double begin, double beats, double now) {
+  GROOVE_NO_CONTRACT
+  const double kThreshold = 0.003981071705534973; // 0x1.04e74cc73ee88p-8
+  double t = (now - begin) / beats;
+  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+  double c;
+  switch (kind) {
+    case GROOVE_CTL_STEP_SLOPE: c = t; break;
+    case GROOVE_CTL_STEP_LOGARITHMIC: c = t < kThreshold ? 0.0 : 1.0 + (5.0 / 12.0) * log10(t); break;
+    case GROOVE_CTL_STEP_EXPONENTIAL: c = t > 1.0 - kThreshold ? 1.0 : -(5.0 / 12.0) * log10(1.0 - t); break;
+    default: return start; // GROOVE_CTL_STEP_FLAT
+  }
+  const double span = end - start;
+  const double rise = span * c;
+  return start + rise;
+}
+
 // ------------------------------------------------------------------ targets
 // groove_fx_set_param's laws where the device form IS the value.  The others are derived on the host in f64 (cutoff, q,
 // passband-ripple -> coefficients; a FILTER link derives them on the device instead, below) or choose a kernel path there
@@ -77,14 +124,23 @@ GROOVE_HD uint32_t ctl_shadow_word(uint32_t control_index) {
   return control_index == GROOVE_CTL_FX_CUTOFF ? CTL_SHADOW_CUTOFF : (control_index == GROOVE_CTL_FX_Q ? CTL_SHADOW_Q : CTL_SHADOW_RIPPLE);
 }
 // value01 (clamped like groove_fx_set_param's) -> the float groove_fx_params would hold
-GROOVE_HD float ctl_derived_param(uint32_t control_index, float value01) {
-  const double v = clamp01d((double)value01);
+GROOVE_HD float ctl_derived_param_f64(uint32_t control_index, double value01) {
+  const double v = clamp01d(value01);
   return control_index == GROOVE_CTL_FX_CUTOFF ? (float)fx_percent_to_frequency(v) : (float)fx_q_law(v);
 }
+GROOVE_HD float ctl_derived_param(uint32_t control_index, float value01) { return ctl_derived_param_f64(control_index, (double)value01); }
 GROOVE_HD bool ctl_target_is_uint(uint32_t control_index) { return control_index == GROOVE_CTL_FX_BITS; }
 GROOVE_HD float ctl_target_float(float value01) { return value01; } // ceiling, threshold, attenuation
 GROOVE_HD uint32_t ctl_target_bits(float value01) {
   const uint32_t b = (uint32_t)(value01 * 16.0f);
+  return b > 31u ? 31u : b;
+}
+// A trip hands on an f64 value that may lie outside 0..1 (a step's start and end are any finite numbers): groove_fx_set_param's clamp,
+// then its law in the precision it has there — (float)v for the float targets, (uint32_t)(v * 16.0) capped like the upload for bits —
+// so that a trip on the device gives the target word the host trip gives it.
+GROOVE_HD float ctl_target_float_f64(double value) { return (float)clamp01d(value); }
+GROOVE_HD uint32_t ctl_target_bits_f64(double value) {
+  const uint32_t b = (uint32_t)(clamp01d(value) * 16.0);
   return b > 31u ? 31u : b;
 }
 

@@ -48,6 +48,29 @@ __global__ __launch_bounds__(kThreads) void ctl_apply_kernel(uint32_t source, Ct
   else dst_f[e] = ctl_target_float(v);
 }
 
+// What a filter link's apply does with the parameter `mine` of lane e: into the lane's word of the parameter shadow, then the lane's
+// coefficients from the five shadow words in f64 (fx_coef.h: the host's own text), stored where the IIR kernels read them, coef[k * n + lane].
+__device__ __forceinline__ void ctl_filter_store(uint32_t kind, uint32_t control_index, float mine, double sr, float* __restrict__ shadow,
+                                                 double* __restrict__ coef, uint32_t n, uint32_t e) {
+  const uint32_t word = ctl_shadow_word(control_index);
+  shadow[(size_t)word * n + e] = mine;
+  float p[CTL_SHADOW_WORDS];
+#pragma unroll
+  for (uint32_t k = 0; k < CTL_SHADOW_WORDS; ++k) p[k] = k == word ? mine : shadow[(size_t)k * n + e];
+  double c[6];
+  uint32_t nc = 5;
+  if (kind == GROOVE_FX_BIQUAD_LP24) {
+    fx_lp24_coeffs((double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_RIPPLE], sr, c);
+    nc = 6;
+  } else if (!fx_rbj_for_kind(kind, (double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_Q], (double)p[CTL_SHADOW_BANDWIDTH],
+                              (double)p[CTL_SHADOW_DB_GAIN], sr, c)) {
+    return; // (not an IIR kind: groove_ctl_filter_link_create refuses it)
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 6; ++k)
+    if (k < nc) coef[(size_t)k * n + e] = c[k];
+}
+
 // A link onto a filter's cutoff, q or passband-ripple (ctl_target_derived): the control value becomes the parameter by
 // groove_fx_set_param's law, lands in the lane's word of the parameter shadow, and the lane's coefficients are derived from the five
 // shadow words in f64 (fx_coef.h: the host's own text) and stored where the IIR kernels read them, coef[k * n + lane].  A second link
@@ -66,24 +89,46 @@ __global__ __launch_bounds__(kThreads) void ctl_filter_apply_kernel(uint32_t sou
     if (*captured == 0u) return;
     v = ctl_signal_value01(src.law[s], value[s]);
   }
-  const uint32_t word = ctl_shadow_word(control_index);
-  const float mine = ctl_derived_param(control_index, v);
-  shadow[(size_t)word * n + e] = mine;
-  float p[CTL_SHADOW_WORDS];
-#pragma unroll
-  for (uint32_t k = 0; k < CTL_SHADOW_WORDS; ++k) p[k] = k == word ? mine : shadow[(size_t)k * n + e];
-  double c[6];
-  uint32_t nc = 5;
-  if (kind == GROOVE_FX_BIQUAD_LP24) {
-    fx_lp24_coeffs((double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_RIPPLE], sr, c);
-    nc = 6;
-  } else if (!fx_rbj_for_kind(kind, (double)p[CTL_SHADOW_CUTOFF], (double)p[CTL_SHADOW_Q], (double)p[CTL_SHADOW_BANDWIDTH],
-                              (double)p[CTL_SHADOW_DB_GAIN], sr, c)) {
-    return; // (not an IIR kind: groove_ctl_filter_link_create refuses it)
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 6; ++k)
-    if (k < nc) coef[(size_t)k * n + e] = c[k];
+  ctl_filter_store(kind, control_index, ctl_derived_param(control_index, v), sr, shadow, coef, n, e);
+}
+
+// ---- trip source --------------------------------------------------------------------------------------------------------------
+// The device table of a trip link, SoA [step][source lane]: begin has n_steps + 1 rows (ctl_core.h: ctl_trip_begins).
+struct CtlTrip {
+  const double* __restrict__ begin;
+  const double* __restrict__ start;
+  const double* __restrict__ end;
+  const double* __restrict__ beats;
+  const uint32_t* __restrict__ kind;
+  uint32_t n_steps;
+};
+// The value of source lane s at `now`, or false where the lane's trip has no step there.
+__device__ __forceinline__ bool ctl_trip_lane_value(const CtlTrip& t, uint32_t n_src, uint32_t s, double now, double& v) {
+  const int32_t i = ctl_trip_find(t.begin + s, n_src, t.n_steps, now);
+  if (i < 0) return false;
+  const size_t at = (size_t)i * n_src + s;
+  v = ctl_trip_value(t.kind[at], t.start[at], t.end[at], t.begin[at], t.beats[at], now);
+  return true;
+}
+// ctl_apply_kernel with a trip as the source: the f64 value through groove_fx_set_param's law (ctl_core.h: ctl_target_*_f64).
+__global__ __launch_bounds__(kThreads) void ctl_trip_apply_kernel(CtlTrip trip, uint32_t n_src, uint64_t at_units, float* __restrict__ dst_f,
+                                                                  uint32_t* __restrict__ dst_u, uint32_t n) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= n) return;
+  double v;
+  if (!ctl_trip_lane_value(trip, n_src, n_src == 1u ? 0u : e, ctl_trip_now(at_units), v)) return;
+  if (dst_u) dst_u[e] = ctl_target_bits_f64(v);
+  else dst_f[e] = ctl_target_float_f64(v);
+}
+// ctl_filter_apply_kernel with a trip as the source.
+__global__ __launch_bounds__(kThreads) void ctl_trip_filter_apply_kernel(CtlTrip trip, uint32_t n_src, uint64_t at_units, uint32_t kind,
+                                                                         uint32_t control_index, double sr, float* __restrict__ shadow,
+                                                                         double* __restrict__ coef, uint32_t n) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= n) return;
+  double v;
+  if (!ctl_trip_lane_value(trip, n_src, n_src == 1u ? 0u : e, ctl_trip_now(at_units), v)) return;
+  ctl_filter_store(kind, control_index, ctl_derived_param_f64(control_index, v), sr, shadow, coef, n, e);
 }
 
 } // namespace groove

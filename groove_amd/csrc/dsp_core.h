@@ -29,6 +29,13 @@
 #else
 #define GROOVE_HD inline
 #endif
+// First statement of a function whose products and sums must each be rounded by themselves, as the host's build rounds them: device code
+// is built with contraction on, and a fused a + b * c does not give the host's bits (fx_coef.h, ctl_core.h: one text for both sides).
+#if defined(__clang__)
+#define GROOVE_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define GROOVE_NO_CONTRACT
+#endif
 
 namespace groove {
 

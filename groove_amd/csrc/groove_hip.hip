@@ -183,6 +183,10 @@ struct groove_ctl_link {
   uint64_t* d_lanes = nullptr; // delta64[n_src], duty64[n_src], then waveform[n_src], law[n_src] as uint32
   float* d_value = nullptr;    // [n_src] captured samples (signal source)
   uint32_t* d_captured = nullptr;
+  // a trip link (groove_ctl_trip_create): begin[n_steps + 1][n_src], start, end, beats [n_steps][n_src] as f64, then kind[n_steps][n_src]
+  // as uint32 — uploaded once: nothing in it depends on the sample rate
+  double* d_trip = nullptr;
+  uint32_t n_steps = 0;
 };
 
 // Events that only order the library's own streams on one device: no timing, and no system-scope fence
@@ -1322,8 +1326,8 @@ int groove_update_sample_rate(groove_ctx* ctx, uint32_t hz) {
     if (fx_setup_state(fx)) return 1;
     if (fx_upload_params(fx)) return 1;
   }
-  for (groove_ctl_link* l : ctx->links) // an LFO's increment is f / SR
-    if (ctl_upload_lanes(l)) return 1;
+  for (groove_ctl_link* l : ctx->links) // an LFO's increment is f / SR (a trip's table is in beats: it stays)
+    if (l->source != GROOVE_CTL_SRC_TRIP && ctl_upload_lanes(l)) return 1;
   return 0;
 }
 int groove_event_create(groove_ctx* ctx, void** out_event) {
@@ -2795,6 +2799,7 @@ int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t fram
   if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
   groove_ctx* ctx = l->ctx;
   if (blk->ctx != ctx) return fail(ctx, "groove_ctl_link_capture: link and block belong to different contexts");
+  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_capture: a trip link captures nothing (groove_ctl_trip_apply is its only call)");
   if (l->source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_capture: not a signal link");
   if (blk->n != l->n_src) return fail(ctx, "groove_ctl_link_capture: block lanes != source lanes");
   if (frames > blk->cap) return fail(ctx, "groove_ctl_link_capture: frames > block capacity");
@@ -2810,6 +2815,7 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   if (!l) return fail(nullptr, "groove_ctl_link_apply: link is NULL");
   groove_ctx* ctx = l->ctx;
   groove_fx* fx = l->target;
+  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_apply: a trip link is applied at a musical time: use groove_ctl_trip_apply");
   if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_apply: the target effect has been destroyed");
   GHIP(ctx, hipSetDevice(ctx->device));
   if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
@@ -2828,9 +2834,104 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+// A trip link: ONE create for the plain and the filter form, by the parameter.
+int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                           groove_fx* target, uint32_t control_index, groove_ctl_link** out) {
+  if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, "groove_ctl_trip_create: NULL argument");
+  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, "groove_ctl_trip_create: the target is not a live effect of this context");
+  if (n_src != 1 && n_src != target->n) return fail(ctx, "groove_ctl_trip_create: n_src must be the target's lane count, or 1 (broadcast)");
+  bool derived = false;
+  switch (control_index) {
+    case GROOVE_CTL_FX_WET:
+      return fail(ctx, "groove_ctl_trip_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE:
+      if (!ctl_target_derived(target->kind, control_index))
+        return fail(ctx, "groove_ctl_trip_create: the target's kind has no such parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)");
+      derived = true;
+      break;
+    default: {
+      if (!ctl_target_linkable(control_index)) return fail(ctx, "groove_ctl_trip_create: unknown control index");
+      const bool fits = (control_index == GROOVE_CTL_FX_CEILING && target->kind == GROOVE_FX_GAIN) ||
+                        (control_index == GROOVE_CTL_FX_BITS && target->kind == GROOVE_FX_BITCRUSHER) ||
+                        (control_index == GROOVE_CTL_FX_ATTENUATION && target->kind == GROOVE_FX_REVERB) ||
+                        (control_index == GROOVE_CTL_FX_THRESHOLD && (target->kind == GROOVE_FX_COMPRESSOR || target->kind == GROOVE_FX_LIMITER));
+      if (!fits) return fail(ctx, "groove_ctl_trip_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
+    }
+  }
+  if (n_steps == 0) return fail(ctx, "groove_ctl_trip_create: a trip has at least one step");
+  if (n_steps > 65536u) return fail(ctx, "groove_ctl_trip_create: more than 65,536 steps");
+  for (uint32_t s = 0; s < n_src; ++s) {
+    if (!std::isfinite(start_beat[s])) return fail(ctx, "groove_ctl_trip_create: start_beat is not finite");
+    for (uint32_t i = 0; i < n_steps; ++i) {
+      const groove_ctl_step& st = steps[(size_t)s * n_steps + i];
+      if (!ctl_trip_kind_ok(st.kind)) return fail(ctx, "groove_ctl_trip_create: unknown step kind (flat, slope, logarithmic, exponential; `Triggered` has no behaviour)");
+      if (!std::isfinite(st.beats) || !std::isfinite(st.start) || !std::isfinite(st.end)) return fail(ctx, "groove_ctl_trip_create: a step's beats, start or end is not finite");
+      if (!(st.beats > 0.0)) return fail(ctx, "groove_ctl_trip_create: a step's beats must be > 0");
+    }
+  }
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (derived && !target->d_shadow) { // the first filter link onto this effect: from here on fx_upload_params keeps the shadow beside the coefficients
+    if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
+      target->d_shadow = nullptr;
+      return fail(ctx, "groove_ctl_trip_create: hipMalloc failed");
+    }
+    if (fx_acquire_ctx(target) || fx_upload_shadow(target)) return 1;
+  }
+  // the table, SoA [step][source lane]
+  const size_t rows = (size_t)n_steps * n_src, doubles = rows * 4 + n_src;
+  std::vector<double> w(doubles + (rows + 1) / 2);
+  double *begin = w.data(), *start = begin + rows + n_src, *end = start + rows, *beats = end + rows;
+  uint32_t* kind = reinterpret_cast<uint32_t*>(beats + rows);
+  for (uint32_t s = 0; s < n_src; ++s) {
+    const groove_ctl_step* st = steps + (size_t)s * n_steps;
+    for (uint32_t i = 0; i < n_steps; ++i) {
+      const size_t at = (size_t)i * n_src + s;
+      start[at] = st[i].start; end[at] = st[i].end; beats[at] = st[i].beats; kind[at] = st[i].kind;
+    }
+    ctl_trip_begins(start_beat[s], beats + s, n_src, n_steps, begin + s, n_src);
+  }
+  groove_ctl_link* l = new groove_ctl_link();
+  l->ctx = ctx; l->source = GROOVE_CTL_SRC_TRIP; l->n_src = n_src; l->control_index = control_index; l->target = target; l->derived = derived;
+  l->n_steps = n_steps;
+  if (hipMalloc(&l->d_trip, w.size() * 8) != hipSuccess) {
+    l->d_trip = nullptr;
+    groove_ctl_link_destroy(l);
+    return fail(ctx, "groove_ctl_trip_create: hipMalloc failed");
+  }
+  if (ctx_memcpy(ctx, l->d_trip, w.data(), w.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, "groove_ctl_trip_create: the upload of the step table failed");
+  }
+  ctx->links.push_back(l);
+  *out = l;
+  return 0;
+}
+int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
+  if (!l) return fail(nullptr, "groove_ctl_trip_apply: link is NULL");
+  groove_ctx* ctx = l->ctx;
+  groove_fx* fx = l->target;
+  if (l->source != GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_trip_apply: not a trip link (an LFO or signal link is applied at a frame: groove_ctl_link_apply)");
+  if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_trip_apply: the target effect has been destroyed");
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
+  const size_t rows = (size_t)l->n_steps * l->n_src;
+  const double *begin = l->d_trip, *start = begin + rows + l->n_src, *end = start + rows, *beats = end + rows;
+  const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
+  if (l->derived) {
+    hipLaunchKernelGGL(ctl_trip_filter_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, fx->kind, l->control_index,
+                       (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n);
+  } else {
+    const bool as_uint = ctl_target_is_uint(l->control_index);
+    hipLaunchKernelGGL(ctl_trip_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, as_uint ? nullptr : fx->d_fa,
+                       as_uint ? fx->d_ua : nullptr, fx->n);
+  }
+  GHIP(ctx, hipGetLastError());
+  return 0;
+}
 int groove_ctl_link_reset(groove_ctl_link* l) {
   if (!l) return fail(nullptr, "groove_ctl_link_reset: link is NULL");
   groove_ctx* ctx = l->ctx;
+  if (l->source == GROOVE_CTL_SRC_TRIP) return 0; // a closed form of musical time: nothing to forget
   GHIP(ctx, hipSetDevice(ctx->device));
   GHIP(ctx, hipMemsetAsync(l->d_captured, 0, 4, ctx->stream));
   return 0;
@@ -2841,7 +2942,7 @@ int groove_ctl_link_destroy(groove_ctl_link* l) {
   (void)hipStreamSynchronize(ctx->stream); // the link's kernels run there
   auto it = std::find(ctx->links.begin(), ctx->links.end(), l);
   if (it != ctx->links.end()) ctx->links.erase(it);
-  (void)hipFree(l->d_lanes); (void)hipFree(l->d_value); (void)hipFree(l->d_captured);
+  (void)hipFree(l->d_lanes); (void)hipFree(l->d_value); (void)hipFree(l->d_captured); (void)hipFree(l->d_trip);
   delete l;
   return 0;
 }

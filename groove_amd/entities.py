@@ -454,3 +454,31 @@ class ControlLink:
         if self.h:
             self.ctx.L.groove_ctl_link_destroy(self.h)
             self.h = None
+
+
+class ControlTripLink:
+    """A control trip linked to one parameter of an Effect, resident on the device (groove_ctl_trip_create): `lanes` is one list of
+    steps (kind, start, end, beats) per source lane — one lane for every target lane, or one for all — and `start_beats` the lanes'
+    start beats (a number: the same for all).  work(at_units) is IsController.work for the block that starts at that musical time,
+    abi_types.CTL_UNITS_PER_BEAT units per beat."""
+
+    def __init__(self, ctx, lanes, start_beats, target, control_index):
+        self.ctx, self.target, self.n_src = ctx, target, len(lanes)
+        steps, n_steps = T.ctl_steps(lanes)
+        if not isinstance(start_beats, (list, tuple)):
+            start_beats = [start_beats] * len(lanes)
+        starts = (C.c_double * len(lanes))(*start_beats)
+        h = C.c_void_p()
+        _lib.check(ctx.L.groove_ctl_trip_create(ctx.h, steps, n_steps, starts, len(lanes), target.h, control_index, C.byref(h)), ctx.h)
+        self.h = h
+
+    def work(self, at_units):
+        _lib.check(self.ctx.L.groove_ctl_trip_apply(self.h, at_units), self.ctx.h)
+
+    def reset(self):
+        _lib.check(self.ctx.L.groove_ctl_link_reset(self.h), self.ctx.h)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.L.groove_ctl_link_destroy(self.h)
+            self.h = None

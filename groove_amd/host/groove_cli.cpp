@@ -1,10 +1,12 @@
 // groove-cli-hip — offline renderer, the GPU-path counterpart of the reference's `groove-cli`
 // (/root/reference/src/bin/groove-cli.rs:24-53 args, :56-158 main; gated at the reference commit).
 //
-//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--quiet] [--perf] [--debug] FILE...
+//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--quiet] [--perf] [--debug] FILE...
 //
 // --device-filter-links: `controls` onto a filter's cutoff, q or passband-ripple stay on the device (Orchestrator::set_filter_links_on_device),
 // a signal source's among them, which are dropped with a warning otherwise.
+// --device-trips: control trips onto effect parameters the library can reach stay on the device (Orchestrator::set_trips_on_device): no
+// host wait per automated block.
 //
 // For each project file: SongSettings::new_from_project_file → instantiate → update_sample_rate(44100)
 // → run_performance(buffer) → (with --wav) send_performance_to_file(<input with .json5/.json → .wav>).
@@ -27,7 +29,7 @@ static std::string wav_name(const std::string& in) {
 }
 
 int main(int argc, char** argv) {
-  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false;
+  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false;
   int device = 0;
   std::string assets = "assets";
   std::vector<std::string> inputs;
@@ -39,11 +41,12 @@ int main(int argc, char** argv) {
     else if (a == "--debug" || a == "-d") debug = true;
     else if (a == "--synthetic-kit") synthetic = true;
     else if (a == "--device-filter-links") filter_links = true;
+    else if (a == "--device-trips") device_trips = true;
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--version" || a == "-v") { std::printf("groove-cli-hip 0.1 (MI355X render path)\n"); return 0; }
     else if (a == "--help" || a == "-h") {
-      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--quiet] [--perf] [--debug] FILE...\n");
+      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--quiet] [--perf] [--debug] FILE...\n");
       return 0;
     } else inputs.push_back(a);
   }
@@ -61,6 +64,7 @@ int main(int argc, char** argv) {
     Orchestrator o(device, GROOVE_DEFAULT_SAMPLE_RATE, desc.bpm);
     if (!o.ctx()) { std::fprintf(stderr, "no HIP device: %s (this renderer has no CPU path)\n", o.last_error().c_str()); return 1; }
     o.set_filter_links_on_device(filter_links);
+    o.set_trips_on_device(device_trips);
     if (instantiate(o, desc, assets, synthetic)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (!quiet) std::printf("Performing to queue %s\n", in.c_str());
     const auto t0 = std::chrono::steady_clock::now();
@@ -73,6 +77,10 @@ int main(int argc, char** argv) {
       std::printf("Orchestrator performance:\n Elapsed    : %.6f s\n Frames     : %zu\n Samples per msec (goal > %.1f): %.1f\n usec per sample (goal < %.2f): %.4f\n x real time: %.1f\n",
                   secs, frames, perf_out.sample_rate / 1000.0, frames / (secs * 1000.0), 1e6 / perf_out.sample_rate,
                   secs * 1e6 / (frames ? frames : 1), frames / (double)perf_out.sample_rate / secs);
+    }
+    if (debug) { // the library's counters after the run (host_waits, host_wait_ms, ...: groove_debug_info)
+      std::vector<char> info(1 << 16);
+      if (!groove_debug_info(o.ctx(), info.data(), info.size())) std::printf("debug_info: %s\n", info.data());
     }
     if (wav) {
       const std::string out = wav_name(in);

@@ -179,11 +179,24 @@ uint64_t ControlTrip::end_units_() const {
   for (auto& s : steps_) b += s.beats;
   return MusicalTime::from_beats(b).units;
 }
+void ControlTrip::set_device_link(groove_ctl_link* link) {
+  if (dev_) groove_ctl_link_destroy(dev_);
+  dev_ = link;
+  last_step_ = -1;
+}
 void ControlTrip::work(uint64_t start_units, uint64_t end_units, std::vector<MidiEvent>&, Orchestrator& o) {
   (void)end_units;
   const double now = (double)start_units / MusicalTime::UNITS_IN_BEAT; // block-granular: value at block start
   double b = start_;
+  int i = 0;
   for (auto& s : steps_) {
+    if (dev_ && now >= b && now < b + s.beats) {
+      // the link's kernel finds the step again and evaluates it; a FLAT step it has already been given holds nothing new (the host trip's
+      // "sent when it changes", for the one case that is known without evaluating anything)
+      if (s.kind != ControlStep::FLAT || i != last_step_) o.control_link(dev_, start_units, true);
+      last_step_ = i;
+      return;
+    }
     if (now >= b && now < b + s.beats) {
       const double v = value_at(s, (now - b) / s.beats);
       if (v != last_sent_) {
@@ -193,6 +206,7 @@ void ControlTrip::work(uint64_t start_units, uint64_t end_units, std::vector<Mid
       return;
     }
     b += s.beats;
+    ++i;
   }
 }
 
@@ -403,6 +417,46 @@ void Orchestrator::skip_to_start() {
   frames_ = 0; performing_ = true; ahead_primed_ = false; deferred_.clear();
   for (auto& n : nodes_)
     if (n.entity && n.entity->control_source()) n.entity->control_source()->reset_controls();
+  place_trips();
+}
+void Orchestrator::place_trips() {
+  std::vector<ControlTrip*> trips;
+  for (auto& n : nodes_)
+    if (n.entity && n.entity->control_trip()) trips.push_back(n.entity->control_trip());
+  for (ControlTrip* t : trips) t->set_device_link(nullptr); // decided anew for every performance: the switch and the links may have changed
+  if (!trips_on_device_) return;
+  auto fx_of = [&](Uid target) -> groove_fx* {
+    Entity* e = get(target);
+    return e && e->is_effect() ? static_cast<Effect*>(e)->library_fx() : nullptr;
+  };
+  auto reachable = [&](const ControlTrip* t) {
+    if (!fx_of(t->target()) || t->steps().empty()) return false;
+    const uint32_t kind = static_cast<FxEffect*>(get(t->target()))->kind();
+    return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index());
+  };
+  // the effects that ANY control reaches through the host: a trip the library cannot take, a `controls` link without a device link
+  std::vector<char> host_path(nodes_.size(), 0);
+  for (ControlTrip* t : trips)
+    if (t->target() < nodes_.size() && !reachable(t)) host_path[t->target()] = 1;
+  for (auto& n : nodes_)
+    if (n.entity && n.entity->control_source())
+      for (const ControlSource::Link& l : n.entity->control_source()->link_list())
+        if (!l.dev && l.target < nodes_.size()) host_path[l.target] = 1;
+  for (ControlTrip* t : trips) {
+    if (t->target() >= nodes_.size() || host_path[t->target()]) continue;
+    std::vector<groove_ctl_step> steps;
+    for (const ControlStep& s : t->steps()) steps.push_back({(uint32_t)s.kind, s.start, s.end, s.beats});
+    const double start = t->start_beat();
+    groove_ctl_link* link = nullptr;
+    if (groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
+      // the library has the last word (a step it refuses: zero beats, a Triggered step): this effect's trips all stay on the host
+      host_path[t->target()] = 1;
+      for (ControlTrip* u : trips)
+        if (u->target() == t->target()) u->set_device_link(nullptr);
+      continue;
+    }
+    t->set_device_link(link);
+  }
 }
 int Orchestrator::link_control(Uid source, Uid target, const std::string& param) {
   Entity* se = get(source);
@@ -434,9 +488,9 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
   src->add_link({nullptr, target, (uint32_t)idx});
   return 0;
 }
-int Orchestrator::control_link(groove_ctl_link* link, uint64_t at_frame) {
-  if (deferring_) { deferred_.push_back({0, 0, 0.0, link, at_frame}); return 0; }
-  if (groove_ctl_link_apply(link, at_frame)) return fail(groove_last_error(ctx_));
+int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units) {
+  if (deferring_) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
+  if (trip_units ? groove_ctl_trip_apply(link, at) : groove_ctl_link_apply(link, at)) return fail(groove_last_error(ctx_));
   return 0;
 }
 int Orchestrator::control_effect(Uid target, uint32_t index, double value01) {
@@ -447,7 +501,7 @@ int Orchestrator::control_effect(Uid target, uint32_t index, double value01) {
     if (static_cast<Instrument*>(e)->control_set_param(index, value01)) return fail(groove_last_error(ctx_));
     return 0;
   }
-  if (deferring_) { deferred_.push_back({target, index, value01, nullptr, 0}); return 0; }
+  if (deferring_) { deferred_.push_back({target, index, value01, nullptr, 0, false}); return 0; }
   if (e && e->is_effect()) return static_cast<Effect*>(e)->control_set_param(index, value01);
   return 0;
 }
@@ -522,7 +576,7 @@ int Orchestrator::tick_ahead(StereoSample* out, uint32_t frames, uint32_t* ticks
     if (rc) return 1;
     if (out && groove_download(ctx_, bus_, &out[0].l, (size_t)done * 2)) return fail(groove_last_error(ctx_));
     for (const Deferred& d : deferred_) {
-      if (d.link) control_link(d.link, d.at_frame); else control_effect(d.target, d.index, d.value);
+      if (d.link) control_link(d.link, d.at, d.trip_units); else control_effect(d.target, d.index, d.value);
     }
     deferred_.clear();
     frames_ += done; // clock.tick_batch(ticks_completed)
@@ -735,6 +789,12 @@ void gh_unpatch_all(void* h) { ((Orchestrator*)h)->unpatch_all(); }
 void gh_set_render_ahead(void* h, int mode) { ((Orchestrator*)h)->set_render_ahead(mode); }
 void gh_set_fused_direct(void* h, int on) { ((Orchestrator*)h)->set_fused_direct(on != 0); }
 void gh_set_filter_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_filter_links_on_device(on != 0); }
+void gh_set_trips_on_device(void* h, int on) { ((Orchestrator*)h)->set_trips_on_device(on != 0); }
+// 1: the trip has been device-resident since the last skip_to_start (a run's start); 0: it goes through the host (or is no trip)
+int gh_control_trip_on_device(void* h, int uid) {
+  Entity* e = ((Orchestrator*)h)->get((Uid)uid);
+  return e && e->control_trip() && e->control_trip()->on_device() ? 1 : 0;
+}
 // groove_debug_info of the orchestrator's context (a JSON object; it waits for the ctx stream).
 int gh_debug_info(void* h, char* out, size_t cap) { return groove_debug_info(((Orchestrator*)h)->ctx(), out, cap); }
 int gh_connect_midi_downstream(void* h, int uid, int channel) { return ((Orchestrator*)h)->connect_midi_downstream((Uid)uid, (uint8_t)channel); }

@@ -56,6 +56,7 @@ struct MusicalTime {
 
 class Orchestrator;
 class ControlSource;
+class ControlTrip;
 
 class Entity {
  public:
@@ -67,6 +68,7 @@ class Entity {
   virtual bool is_controller() const { return false; }
   // the source side of `controls` links, if the entity is a controller DEVICE (an LFO, a signal passthrough)
   virtual ControlSource* control_source() { return nullptr; }
+  virtual ControlTrip* control_trip() { return nullptr; } // the entity itself, if it is a ControlTrip
 };
 
 // #[derive(Control)] kebab-case names of the effects' parameters (proc-macros/src/control.rs:127-131, 165) -> groove_control_index; -1: none.
@@ -271,10 +273,21 @@ struct ControlStep {
   double start = 0.0, end = 0.0; // FLAT uses start as its value
   double beats = 1.0;            // duration of this step
 };
+// A trip works through Orchestrator::control_effect — one groove_fx_set_param, with its host wait, per block in which the value moves —
+// unless the orchestrator has made it DEVICE-RESIDENT when the performance started (Orchestrator::set_trips_on_device, skip_to_start):
+// then its steps live in the library (groove_ctl_trip_create) and work() only names the block's start time (Orchestrator::control_link).
 class ControlTrip : public Controller {
  public:
   ControlTrip(Uid target, uint32_t control_index, double start_beat) : target_(target), index_(control_index), start_(start_beat) {}
+  ~ControlTrip() override { set_device_link(nullptr); }
+  ControlTrip* control_trip() override { return this; }
   void add_step(const ControlStep& s) { steps_.push_back(s); }
+  Uid target() const { return target_; }
+  uint32_t control_index() const { return index_; }
+  double start_beat() const { return start_; }
+  const std::vector<ControlStep>& steps() const { return steps_; }
+  bool on_device() const { return dev_ != nullptr; }
+  void set_device_link(groove_ctl_link* link); // takes ownership; destroys the link it had
   void work(uint64_t start_units, uint64_t end_units, std::vector<MidiEvent>& out, Orchestrator& o) override;
   bool is_finished(uint64_t end_units) const override { return end_units >= end_units_(); }
   uint64_t end_units() const override { return end_units_(); }
@@ -286,6 +299,8 @@ class ControlTrip : public Controller {
   double start_;
   std::vector<ControlStep> steps_;
   double last_sent_ = -1.0;
+  groove_ctl_link* dev_ = nullptr; // device-resident: the trip link
+  int last_step_ = -1;             // device-resident: the step of the last apply (a FLAT step is applied once)
 };
 
 // ---- controller devices ------------------------------------------------------------------------
@@ -299,6 +314,7 @@ class ControlSource {
   struct Link { groove_ctl_link* dev; Uid target; uint32_t index; }; // dev == nullptr: through Orchestrator::control_effect
   virtual groove_ctl_source source_desc() const = 0;
   void add_link(const Link& l) { links_.push_back(l); }
+  const std::vector<Link>& link_list() const { return links_; }
   size_t links() const { return links_.size(); }
   void work_controls(Orchestrator& o, uint64_t at_frame);
   void reset_controls(); // Resets::reset: a signal source forgets what it captured
@@ -391,9 +407,17 @@ class Orchestrator {
   // with the switch off.  Off by default; it affects the links made after it is set.
   void set_filter_links_on_device(bool on) { filter_links_on_device_ = on; }
   bool filter_links_on_device() const { return filter_links_on_device_; }
-  // A device-resident link's value for the block at `at_frame`: applied now, or — like control_effect — held back while the controllers
-  // are run one block ahead of the effects.
-  int control_link(groove_ctl_link* link, uint64_t at_frame);
+  // A device-resident link's value for the block at `at`: applied now, or — like control_effect — held back while the controllers
+  // are run one block ahead of the effects.  `at` is the block's first frame (an LFO or signal link: groove_ctl_link_apply) or, for a
+  // trip link, its start in musical-time units (groove_ctl_trip_apply).
+  int control_link(groove_ctl_link* link, uint64_t at, bool trip_units = false);
+  // ControlTrips onto effect parameters the library can reach (groove_ctl_trip_create) stay on the device: no groove_fx_set_param, and so
+  // no host wait, per automated block.  Decided for all trips at once when a performance starts (skip_to_start): a trip is device-resident
+  // iff the switch is on, its target is an effect, the library accepts the parameter for that kind, and EVERY other control onto the same
+  // effect (trips and `controls` links) is device-resident too — one host-path groove_fx_set_param re-uploads the host's stale copy of the
+  // parameter the device trip owns.  Everything else (instruments, wet-dry-mix) takes the host path unchanged.  Off by default.
+  void set_trips_on_device(bool on) { trips_on_device_ = on; }
+  bool trips_on_device() const { return trips_on_device_; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -437,10 +461,12 @@ class Orchestrator {
   int render_ahead_ = 1;
   bool fused_direct_ = true;
   bool filter_links_on_device_ = false;
+  bool trips_on_device_ = false;
+  void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block
   bool deferring_ = false;      // controllers are being run for the NEXT block
-  struct Deferred { Uid target; uint32_t index; double value; groove_ctl_link* link; uint64_t at_frame; }; // link set: a device-resident link's apply
+  struct Deferred { Uid target; uint32_t index; double value; groove_ctl_link* link; uint64_t at; bool trip_units; }; // link set: a device-resident link's apply at `at`
   std::vector<Deferred> deferred_;
   uint64_t sequencing_frame_ = 0;
 };

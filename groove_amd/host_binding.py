@@ -27,6 +27,7 @@ def load():
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
+        "gh_set_trips_on_device": (None, [vp, i]), "gh_control_trip_on_device": (i, [vp, i]),
         "gh_debug_info": (i, [vp, C.c_char_p, C.c_size_t]), "gh_connect_midi_downstream": (i, [vp, i, i]),
         "gh_add_timer": (i, [vp, d]), "gh_add_sequencer": (i, [vp]),
         "gh_sequencer_insert": (i, [vp, i, i, i, d, d]), "gh_sequencer_set_end": (i, [vp, i, d]),
@@ -93,6 +94,15 @@ class Orchestrator:
         """Links made from here on onto a filter's cutoff, q or passband-ripple derive the coefficients on the device (no host wait per
         block), from an LFO or a signal source; off (the default): an LFO goes through the host once per block, a signal source is dropped."""
         self.L.gh_set_filter_links_on_device(self.h, 1 if on else 0)
+
+    def set_trips_on_device(self, on):
+        """Control trips onto effect parameters the library can reach stay on the device (no host wait per automated block); decided for
+        all trips when a run starts — control_trip_on_device(uid) says how it went.  Off by default."""
+        self.L.gh_set_trips_on_device(self.h, 1 if on else 0)
+
+    def control_trip_on_device(self, uid):
+        """1: the trip has been device-resident since the last run started; 0: it goes through the host."""
+        return self.L.gh_control_trip_on_device(self.h, uid)
 
     def debug_info(self):
         """groove_debug_info of the orchestrator's context, parsed (it waits for the ctx stream)."""

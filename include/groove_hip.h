@@ -343,6 +343,28 @@ int groove_ctl_link_capture(groove_ctl_link* link, groove_block* block, uint32_t
  * (nothing captured yet, or since a reset: the target is left untouched).  Ordered like groove_fx_set_param — behind every use of
  * the target submitted so far, ahead of every later one.  An error once the target has been destroyed. */
 int groove_ctl_link_apply(groove_ctl_link* link, uint64_t at_frame);
+/* A TRIP link: a control trip (start_beat plus n_steps steps {kind, start, end, beats}, include/groove_types.h) as the source of a
+ * link — a closed form of musical time, evaluated in f64 by the link's kernel (csrc/ctl_core.h: the host trip's law restated).
+ *   steps[n_src][n_steps], start_beat[n_src]: n_src equals the target's lane count, or is 1 and is broadcast; every source lane has the
+ *   same step count and its own steps.  The steps' begins (begin[0] = start_beat, begin[i + 1] = begin[i] + beats[i], in f64) are
+ *   uploaded once; they do not depend on the sample rate.
+ *   control_index: ONE create for both forms — a parameter whose device form is the value (groove_ctl_link_create's list) makes a
+ *   plain link, a filter's cutoff, q or passband-ripple (groove_ctl_filter_link_create's list) a filter link with the parameter shadow.
+ * Refused: _WET; a parameter the target's kind does not have; n_steps == 0 or > 65,536; a step with beats <= 0 or a non-finite
+ * beats, start or end; a non-finite start_beat; an unknown step kind; a target that is not a live effect.
+ * The value is clamped to 0..1 and goes through groove_fx_set_param's law in the precision it has there, so the target word is the one
+ * that call would give it (flat and slope steps: bit for bit; the two curves read log10 from the device's math library).  The link it
+ * returns takes groove_ctl_trip_apply, groove_ctl_link_reset (nothing to forget: a no-op) and groove_ctl_link_destroy;
+ * groove_ctl_link_apply and groove_ctl_link_capture on it are errors, as is groove_ctl_trip_apply on any other link. */
+int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                           groove_fx* target, uint32_t control_index, groove_ctl_link** out);
+/* IsController::work of a trip for the block that starts at musical time `at_units` (GROOVE_CTL_UNITS_PER_BEAT units per beat): each
+ * lane finds the step that holds at_units / 65536 and writes its value; a lane whose trip has no step there (before start_beat, at or
+ * after the end) leaves its target word untouched, as the host trip sends nothing outside its steps.  Ordered like
+ * groove_ctl_link_apply: one launch on the ctx stream, no wait, no copy.  The staleness rule above holds — and where the host trip
+ * re-sends only when its value changes, an apply inside a step ALWAYS writes, so it also restores a linked parameter that a
+ * groove_fx_set_param(s) on the target has overwritten since. */
+int groove_ctl_trip_apply(groove_ctl_link* link, uint64_t at_units);
 /* Resets::reset (Orchestrator::skip_to_start, orchestrator.rs:971-983): a signal link forgets what it captured. */
 int groove_ctl_link_reset(groove_ctl_link* link);
 /* Orchestrator::unlink_control (orchestrator.rs:1296-1320).  groove_shutdown frees the links that are still alive. */

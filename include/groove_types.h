@@ -193,7 +193,8 @@ typedef enum {
  * as the SOURCE of a control link, groove_ctl_link_create.  docs/DSP_SPEC.md section 13 defines the value laws. */
 typedef enum {
   GROOVE_CTL_SRC_LFO = 0,   /* "lfo"{waveform, frequency}: an oscillator of DSP_SPEC section 2, read once per block     */
-  GROOVE_CTL_SRC_SIGNAL = 1 /* "signal-passthrough-controller": the last frame of the block it has passed on            */
+  GROOVE_CTL_SRC_SIGNAL = 1, /* "signal-passthrough-controller": the last frame of the block it has passed on           */
+  GROOVE_CTL_SRC_TRIP = 2    /* a control trip (groove_ctl_trip_create): a path of steps, a closed form of musical time  */
 } groove_ctl_source_kind;
 /* How a captured sample m in [-1, 1] becomes a ControlValue in 0..1 (signal sources only). */
 typedef enum {
@@ -209,6 +210,22 @@ typedef struct {
   double frequency_hz; /* LFO rate                                                                                      */
   uint32_t law;        /* groove_ctl_law                                                                                */
 } groove_ctl_source;
+
+/* A control trip (ControlTrip, entities/src/controllers/control_trip.rs): automation of one parameter along a path of steps.
+ * The kinds in the order of the host layer's ControlStep::Kind; `Triggered` has no behaviour in the reference and no number here. */
+typedef enum {
+  GROOVE_CTL_STEP_FLAT = 0,        /* `start` for the whole step                                     */
+  GROOVE_CTL_STEP_SLOPE = 1,       /* start + (end - start) * t                                      */
+  GROOVE_CTL_STEP_LOGARITHMIC = 2, /* ... * (t < 10^(-12/5) ? 0 : 1 + 5/12 log10 t)   (MMA convex)  */
+  GROOVE_CTL_STEP_EXPONENTIAL = 3  /* ... * (t > 1 - 10^(-12/5) ? 1 : -5/12 log10(1 - t)) (concave) */
+} groove_ctl_step_kind;
+typedef struct {
+  uint32_t kind; /* groove_ctl_step_kind                          */
+  double start;  /* value at t = 0 (a flat step's value)          */
+  double end;    /* value at t = 1                                */
+  double beats;  /* duration of the step, > 0                     */
+} groove_ctl_step;
+#define GROOVE_CTL_UNITS_PER_BEAT 65536 /* MusicalTime::UNITS_IN_BEAT: groove_ctl_trip_apply's time is in these */
 
 #ifdef __cplusplus
 }
