@@ -144,4 +144,32 @@ GROOVE_HD uint32_t ctl_target_bits_f64(double value) {
   return b > 31u ? 31u : b;
 }
 
+// ------------------------------------------------------------------ targets on a Welsh bank
+// A BANK link (groove_ctl_bank_link_create / groove_ctl_bank_trip_create) reaches the three controls groove_bank_set_param has, by that
+// call's own laws in the precision they have there: the float groove_welsh_params would hold.
+GROOVE_HD bool ctl_bank_target_ok(uint32_t control_index) {
+  return control_index == GROOVE_CTL_WELSH_DCA_GAIN || control_index == GROOVE_CTL_WELSH_DCA_PAN || control_index == GROOVE_CTL_WELSH_CUTOFF;
+}
+GROOVE_HD float ctl_bank_gain_f64(double value) { return (float)clamp01d(value); }
+GROOVE_HD float ctl_bank_pan_f64(double value) { // ControlValue 0..1 -> BipolarNormal
+  GROOVE_NO_CONTRACT
+  const double twice = clamp01d(value) * 2.0;
+  return (float)(twice - 1.0);
+}
+GROOVE_HD float ctl_bank_cutoff_f64(double value) { return (float)fx_percent_to_frequency(clamp01d(value)); } // WelshParams::cutoff_hz
+GROOVE_HD float ctl_bank_param_f64(uint32_t control_index, double value) {
+  return control_index == GROOVE_CTL_WELSH_DCA_GAIN ? ctl_bank_gain_f64(value)
+                                                    : (control_index == GROOVE_CTL_WELSH_DCA_PAN ? ctl_bank_pan_f64(value) : ctl_bank_cutoff_f64(value));
+}
+// dca gain x pan law -> the per-channel gains a voice's last multiply reads (WelshParams / FmParams: gl, gr).  derive_welsh and derive_fm
+// (derive.h) call this with the floats of the public params widened; a bank link's kernel with the floats of the bank's (gain, pan)
+// shadow.  Every product and sum is rounded by itself, on both sides.
+GROOVE_HD void pan_gains(double gain, double pan, float& gl, float& gr) {
+  GROOVE_NO_CONTRACT
+  gl = (float)(gain * (1.0 - 0.25 * (pan + 1.0) * (pan + 1.0)));
+  gr = (float)(gain * (1.0 - (0.5 * pan - 0.5) * (0.5 * pan - 0.5)));
+}
+// The bank's (gain, pan) shadow on the device, [word][lane] in internal lane order (groove_bank: d_dca).
+enum : uint32_t { CTL_DCA_GAIN = 0, CTL_DCA_PAN = 1, CTL_DCA_WORDS = 2 };
+
 } // namespace groove

@@ -4,7 +4,8 @@
 // signal passthrough has passed on, the apply kernel computes the control value (ctl_core.h) and writes it into the
 // target's per-lane parameter array — the same d_fa / d_ua words the effect kernels read — both on the ctx stream, where
 // stream order is the order of the calls.  One thread per lane, kThreads per workgroup like the other per-lane kernels
-// (kernels.h); a launch of either is a few wavefronts and all latency.
+// (kernels.h); a launch of either is a few wavefronts and all latency.  A link onto a Welsh BANK (dca-gain, dca-pan, filter-cutoff) writes
+// the voices' parameter words instead: the last section below.
 #pragma once
 #include "kernels.h"
 #include "ctl_core.h"
@@ -129,6 +130,80 @@ __global__ __launch_bounds__(kThreads) void ctl_trip_filter_apply_kernel(CtlTrip
   double v;
   if (!ctl_trip_lane_value(trip, n_src, n_src == 1u ? 0u : e, ctl_trip_now(at_units), v)) return;
   ctl_filter_store(kind, control_index, ctl_derived_param_f64(control_index, v), sr, shadow, coef, n, e);
+}
+
+// ---- bank target --------------------------------------------------------------------------------------------------------------
+// A link onto a Welsh bank's dca-gain, dca-pan or filter-cutoff (groove_ctl_bank_link_create / groove_ctl_bank_trip_create).  The ONE
+// source lane's value is broadcast to every voice, so voices that shared a parameter record before the apply share one after it: the
+// wave-uniform kernels' records stay uniform.  The voice kernels read these words in two places and both are written here:
+//   params[word * n + lane]   the per-lane SoA (per-lane, time-parallel and note-event kernels)
+//   waves[w].p                the per-virtual-wave copy (wave-uniform kernels), w < n_vwaves; 0 waves on the per-lane form
+// gl and gr depend on gain AND pan, which may differ between the voices of a bank: dca[CTL_DCA_WORDS][n] is the bank's per-lane shadow
+// of the two (internal lane order), the apply stores its own word there and reads the other.
+//
+// This is a BETWEEN-BLOCKS mutation: the host orders the launch behind every render of the bank submitted so far and ahead of every
+// later one (groove_hip.hip bank_link_apply: event join, fork), so no wavefront reads a record while it is written.  A write in the
+// middle of a block would break the promise of welsh_wave_tables_up (kernels.h) — what a wave is at the start of a block it stays for the
+// whole block: its record is in scalar registers, its tables are filled from it — and a padding wave that read a torn record is how a
+// render once never finished (README.md on the stall of rounds 2-3).
+struct CtlBank {
+  uint32_t* __restrict__ params;
+  WaveDesc* __restrict__ waves;
+  float* __restrict__ dca; // nullptr on a cutoff link
+  uint32_t n, n_vwaves, control_index;
+};
+// Thread e serves lane e (e < n) and virtual wave e (e < n_vwaves) with the parameter `mine`, the same in every thread.  A wave's lanes
+// share a record, so the wave's words are those of its lane vbase; only the shadow word this link does NOT write is read from another
+// lane's column, so the two halves need no order between them.  A padding wave (count == 0) is written like any other: its vbase is a
+// valid voice of its kind and nothing reads its gains.
+__device__ __forceinline__ void ctl_bank_store(const CtlBank& b, float mine, uint32_t e) {
+  constexpr uint32_t kGl = offsetof(WelshParams, gl) / 4, kGr = offsetof(WelshParams, gr) / 4, kHz = offsetof(WelshParams, cutoff_hz) / 4;
+  const size_t n = b.n;
+  if (b.control_index == GROOVE_CTL_WELSH_CUTOFF) {
+    if (e < b.n) b.params[kHz * n + e] = __float_as_uint(mine);
+    if (e < b.n_vwaves) b.waves[e].p.cutoff_hz = mine;
+    return;
+  }
+  const bool is_gain = b.control_index == GROOVE_CTL_WELSH_DCA_GAIN;
+  const float* other = b.dca + (size_t)(is_gain ? CTL_DCA_PAN : CTL_DCA_GAIN) * n;
+  if (e < b.n) {
+    b.dca[(size_t)(is_gain ? CTL_DCA_GAIN : CTL_DCA_PAN) * n + e] = mine;
+    float gl, gr;
+    pan_gains((double)(is_gain ? mine : other[e]), (double)(is_gain ? other[e] : mine), gl, gr);
+    b.params[kGl * n + e] = __float_as_uint(gl);
+    b.params[kGr * n + e] = __float_as_uint(gr);
+  }
+  if (e < b.n_vwaves) {
+    const uint32_t lane = b.waves[e].vbase;
+    if (lane < b.n) {
+      float gl, gr;
+      pan_gains((double)(is_gain ? mine : other[lane]), (double)(is_gain ? other[lane] : mine), gl, gr);
+      b.waves[e].p.gl = gl;
+      b.waves[e].p.gr = gr;
+    }
+  }
+}
+// An LFO or signal source: the fp32 value01 widened, through groove_bank_set_param's law.
+__global__ __launch_bounds__(kThreads) void ctl_bank_apply_kernel(uint32_t source, CtlLanes src, uint64_t at_frame, const float* __restrict__ value,
+                                                                  const uint32_t* __restrict__ captured, CtlBank bank) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= bank.n && e >= bank.n_vwaves) return;
+  float v;
+  if (source == GROOVE_CTL_SRC_LFO) {
+    v = ctl_lfo_value01(src.waveform[0], src.delta64[0], src.duty64[0], at_frame);
+  } else {
+    if (*captured == 0u) return;
+    v = ctl_signal_value01(src.law[0], value[0]);
+  }
+  ctl_bank_store(bank, ctl_bank_param_f64(bank.control_index, (double)v), e);
+}
+// A trip source: the f64 value.  No step at at_units: every word stays as it is.
+__global__ __launch_bounds__(kThreads) void ctl_trip_bank_apply_kernel(CtlTrip trip, uint64_t at_units, CtlBank bank) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= bank.n && e >= bank.n_vwaves) return;
+  double v;
+  if (!ctl_trip_lane_value(trip, 1u, 0u, ctl_trip_now(at_units), v)) return;
+  ctl_bank_store(bank, ctl_bank_param_f64(bank.control_index, v), e);
 }
 
 } // namespace groove

@@ -6,6 +6,7 @@
 #pragma once
 #include "dsp_core.h"
 #include "fx_coef.h"
+#include "ctl_core.h"
 
 namespace groove {
 
@@ -30,10 +31,7 @@ inline EnvParams derive_env(const groove_envelope_params& e, double sr) {
 inline uint64_t duty_to_u64(double duty) {
   return (uint64_t)(clamp01_h(duty) * 18446744073709549568.0); // (2^64 - 2048): no overflow at 1.0
 }
-inline void pan_gains(double gain, double pan, float& gl, float& gr) {
-  gl = (float)(gain * (1.0 - 0.25 * (pan + 1.0) * (pan + 1.0)));
-  gr = (float)(gain * (1.0 - (0.5 * pan - 0.5) * (0.5 * pan - 0.5)));
-}
+// (pan_gains — dca gain x pan law -> gl, gr — is ctl_core.h's: the bank links' kernel derives the same two words on the device)
 inline Lp24Consts derive_lp24_consts(double ripple) {
   double sg = sinh(ripple), cg = cosh(ripple);
   cg *= cg;

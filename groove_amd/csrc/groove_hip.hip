@@ -126,6 +126,11 @@ struct groove_bank {
   uint32_t* d_wg_list = nullptr;
   size_t wg_list_cap = 0;
   float* d_pcm = nullptr;   // sampler bank
+  // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
+  // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
+  // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one)
+  float* d_dca = nullptr;
+  uint32_t cutoff_links = 0;
   groove_note_event* d_ev[2] = {nullptr, nullptr};
   // pinned staging of queued note events, two slots in rotation: flush_events hands the events to the ctx
   // stream and returns without a host synchronisation (a project with note events in every block would
@@ -177,7 +182,9 @@ struct groove_fx {
 struct groove_ctl_link {
   groove_ctx* ctx;
   uint32_t source, n_src, control_index;
-  groove_fx* target; // nullptr once the target has been destroyed (groove_fx_destroy clears it)
+  groove_fx* target; // nullptr once the target has been destroyed (groove_fx_destroy clears it), and on a bank link
+  groove_bank* bank = nullptr; // a bank link's target (groove_ctl_bank_link_create); on_bank stays set when groove_bank_destroy clears it
+  bool on_bank = false;
   bool derived = false; // a filter link (groove_ctl_filter_link_create): the apply derives the target lanes' coefficients
   std::vector<groove_ctl_source> src;
   uint64_t* d_lanes = nullptr; // delta64[n_src], duty64[n_src], then waveform[n_src], law[n_src] as uint32
@@ -499,6 +506,19 @@ int upload_soa(groove_ctx* ctx, uint32_t* dst, const std::vector<T>& aos) {
 }
 inline uint32_t blocks_for(size_t items) { return (uint32_t)((items + kThreads - 1) / kThreads); }
 
+// The bank links' (gain, pan) shadow from the host's copy of the parameters, in internal lane order (ctl_link.h: CtlBank::dca).
+int welsh_upload_dca(groove_bank* b) {
+  groove_ctx* ctx = b->ctx;
+  const uint32_t n = b->n;
+  std::vector<float> w((size_t)CTL_DCA_WORDS * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const groove_welsh_params& p = b->welsh[b->plan.perm.empty() ? i : b->plan.perm[i]];
+    w[(size_t)CTL_DCA_GAIN * n + i] = p.dca_gain;
+    w[(size_t)CTL_DCA_PAN * n + i] = p.dca_pan;
+  }
+  GHIP(ctx, ctx_memcpy(ctx, b->d_dca, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
 // Welsh: derive + upload parameters only (SoA, cold values, per-wave table, workgroup lists): derive -> flag -> order -> plan
 // (welsh_plan.h) -> grow -> upload.  `regroup`: the state is (being) reset, so the lane order may be chosen afresh.
 int welsh_upload_params(groove_bank* b, bool regroup) {
@@ -508,12 +528,11 @@ int welsh_upload_params(groove_bank* b, bool regroup) {
   std::vector<WelshParams> Pext(n);
   std::vector<WelshCold> Cext(n);
   for (uint32_t v = 0; v < n; ++v) Pext[v] = derive_welsh(b->welsh[v], sr, Cext[v]);
-  if (ctx->f32_filter) { // WF_FILTER_F32 (derive.h welsh_filter_f32_ok): measured once per distinct filter description
+  { // WF_FILTER_F32 (derive.h welsh_filter_f32_ok): measured once per distinct filter description; none while a link moves the cutoff
     using Key = F32FilterKey;
     if (b->f32_memo_sr != sr) { b->f32_memo.clear(); b->f32_memo_sr = sr; } // (kept across uploads: a control change re-derives the bank, groove_bank_set_param)
     std::map<Key, bool>& memo = b->f32_memo;
-    for (uint32_t v = 0; v < n; ++v) {
-      const WelshParams& o = Pext[v];
+    welsh_flag_filter_f32(Pext, ctx->f32_filter, b->cutoff_links, [&](const WelshParams& o) {
       Key k{};
       k.c0 = o.fc.c0; k.d1 = o.fc.d1; k.c2 = o.fc.c2; k.d3 = o.fc.d3; k.hz = o.cutoff_hz; k.start = o.cutoff_start; k.end = o.cutoff_end;
       k.depth = (o.flags & WF_LFO_CUTOFF) ? o.lfo_depth : 0.0f; k.bits = o.flags & (WF_RETUNE_ENV | WF_LFO_CUTOFF | WF_LFO_RESO | WF_COEF_WIDE);
@@ -521,8 +540,8 @@ int welsh_upload_params(groove_bank* b, bool regroup) {
       // (~0.6 ms per distinct filter description: a bank of more than 4,096 of them — no project of the reference's shape, one patch
       // per synth — keeps the f64 recurrence, always safe, for the descriptions beyond, instead of seconds of measuring at upload)
       if (it == memo.end()) it = memo.emplace(k, memo.size() < 4096 ? welsh_filter_f32_ok(o, sr) : false).first;
-      if (it->second) Pext[v].flags |= WF_FILTER_F32;
-    }
+      return it->second;
+    });
   }
   WelshPlan plan = welsh_plan(Pext, Cext, regroup ? welsh_patch_major_order(Pext) : std::move(b->plan.perm));
   b->plan = std::move(static_cast<WelshLayout&>(plan)); // what the launches read stays with the bank; the arrays of `plan` are uploaded below
@@ -538,6 +557,7 @@ int welsh_upload_params(groove_bank* b, bool regroup) {
   }
   if (upload_soa(ctx, b->d_params, plan.records)) return 1;
   GHIP(ctx, ctx_memcpy(ctx, b->d_cold, plan.cold.data(), plan.cold.size() * 8, hipMemcpyHostToDevice));
+  if (b->d_dca && welsh_upload_dca(b)) return 1; // the bank links' shadow follows the host's copy, in the lane order just decided
   if (plan.waves.empty()) return 0; // the per-lane kernel reads no wave and no list
   const size_t wgs = plan.sorted.list.size(), n_spec = plan.striped.list.size();
   if (b->vwaves_cap < plan.waves.size()) {
@@ -1171,6 +1191,7 @@ void groove_shutdown(groove_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)ctx_join(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  for (groove_ctl_link* l : ctx->links) l->bank = nullptr; // (no bank is re-planned for the links it loses here: it goes next)
   while (!ctx->links.empty()) groove_ctl_link_destroy(ctx->links.back());
   while (!ctx->banks.empty()) groove_bank_destroy(ctx->banks.back());
   while (!ctx->fxs.empty()) groove_fx_destroy(ctx->fxs.back());
@@ -1500,6 +1521,9 @@ int groove_bank_destroy(groove_bank* b) {
   }
   auto it = std::find(ctx->banks.begin(), ctx->banks.end(), b);
   if (it != ctx->banks.end()) ctx->banks.erase(it);
+  for (groove_ctl_link* l : ctx->links) // a link onto this bank has no target any more: its next apply is an error, not a write
+    if (l->bank == b) l->bank = nullptr;
+  (void)hipFree(b->d_dca);
   for (int k = 0; k < 2; ++k) { if (b->h_ev[k]) (void)hipHostFree(b->h_ev[k]); if (b->ev_staged[k]) (void)hipEventDestroy(b->ev_staged[k]); }
   (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
   delete b;
@@ -2705,6 +2729,7 @@ int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, do
 
 // ============================================================================ control links
 // What both kinds of link ask of their arguments and sources, and the link itself once the target has been accepted.
+static int bank_link_apply(groove_ctl_link* l, const char* who, uint64_t at); // (links onto a Welsh bank: below, with their creates)
 static int ctl_link_check(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
   const std::string w = std::string(who) + ": ";
   if (!ctx || !src || !target || !out) return fail(ctx, w + "NULL argument");
@@ -2816,6 +2841,7 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   groove_ctx* ctx = l->ctx;
   groove_fx* fx = l->target;
   if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_apply: a trip link is applied at a musical time: use groove_ctl_trip_apply");
+  if (l->on_bank) return bank_link_apply(l, "groove_ctl_link_apply", at_frame);
   if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_apply: the target effect has been destroyed");
   GHIP(ctx, hipSetDevice(ctx->device));
   if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
@@ -2834,6 +2860,9 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src);
+static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                         uint32_t control_index, groove_ctl_link** out);
 // A trip link: ONE create for the plain and the filter form, by the parameter.
 int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
                            groove_fx* target, uint32_t control_index, groove_ctl_link** out) {
@@ -2858,17 +2887,7 @@ int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32
       if (!fits) return fail(ctx, "groove_ctl_trip_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
     }
   }
-  if (n_steps == 0) return fail(ctx, "groove_ctl_trip_create: a trip has at least one step");
-  if (n_steps > 65536u) return fail(ctx, "groove_ctl_trip_create: more than 65,536 steps");
-  for (uint32_t s = 0; s < n_src; ++s) {
-    if (!std::isfinite(start_beat[s])) return fail(ctx, "groove_ctl_trip_create: start_beat is not finite");
-    for (uint32_t i = 0; i < n_steps; ++i) {
-      const groove_ctl_step& st = steps[(size_t)s * n_steps + i];
-      if (!ctl_trip_kind_ok(st.kind)) return fail(ctx, "groove_ctl_trip_create: unknown step kind (flat, slope, logarithmic, exponential; `Triggered` has no behaviour)");
-      if (!std::isfinite(st.beats) || !std::isfinite(st.start) || !std::isfinite(st.end)) return fail(ctx, "groove_ctl_trip_create: a step's beats, start or end is not finite");
-      if (!(st.beats > 0.0)) return fail(ctx, "groove_ctl_trip_create: a step's beats must be > 0");
-    }
-  }
+  if (ctl_trip_check_steps(ctx, "groove_ctl_trip_create", steps, n_steps, start_beat, n_src)) return 1;
   GHIP(ctx, hipSetDevice(ctx->device));
   if (derived && !target->d_shadow) { // the first filter link onto this effect: from here on fx_upload_params keeps the shadow beside the coefficients
     if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
@@ -2877,6 +2896,33 @@ int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32
     }
     if (fx_acquire_ctx(target) || fx_upload_shadow(target)) return 1;
   }
+  groove_ctl_link* l = nullptr;
+  if (ctl_trip_make(ctx, "groove_ctl_trip_create", steps, n_steps, start_beat, n_src, control_index, &l)) return 1;
+  l->target = target; l->derived = derived;
+  ctx->links.push_back(l);
+  *out = l;
+  return 0;
+}
+// What a trip's create asks of its steps (the effect and the bank form alike).
+static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src) {
+  const std::string w = std::string(who) + ": ";
+  if (n_steps == 0) return fail(ctx, w + "a trip has at least one step");
+  if (n_steps > 65536u) return fail(ctx, w + "more than 65,536 steps");
+  for (uint32_t s = 0; s < n_src; ++s) {
+    if (!std::isfinite(start_beat[s])) return fail(ctx, w + "start_beat is not finite");
+    for (uint32_t i = 0; i < n_steps; ++i) {
+      const groove_ctl_step& st = steps[(size_t)s * n_steps + i];
+      if (!ctl_trip_kind_ok(st.kind)) return fail(ctx, w + "unknown step kind (flat, slope, logarithmic, exponential; `Triggered` has no behaviour)");
+      if (!std::isfinite(st.beats) || !std::isfinite(st.start) || !std::isfinite(st.end)) return fail(ctx, w + "a step's beats, start or end is not finite");
+      if (!(st.beats > 0.0)) return fail(ctx, w + "a step's beats must be > 0");
+    }
+  }
+  return 0;
+}
+// A trip link with its step table on the device and no target yet; the caller sets the target and lists the link.
+static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                         uint32_t control_index, groove_ctl_link** out) {
+  const std::string who_s = std::string(who) + ": ";
   // the table, SoA [step][source lane]
   const size_t rows = (size_t)n_steps * n_src, doubles = rows * 4 + n_src;
   std::vector<double> w(doubles + (rows + 1) / 2);
@@ -2891,18 +2937,17 @@ int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32
     ctl_trip_begins(start_beat[s], beats + s, n_src, n_steps, begin + s, n_src);
   }
   groove_ctl_link* l = new groove_ctl_link();
-  l->ctx = ctx; l->source = GROOVE_CTL_SRC_TRIP; l->n_src = n_src; l->control_index = control_index; l->target = target; l->derived = derived;
+  l->ctx = ctx; l->source = GROOVE_CTL_SRC_TRIP; l->n_src = n_src; l->control_index = control_index; l->target = nullptr;
   l->n_steps = n_steps;
   if (hipMalloc(&l->d_trip, w.size() * 8) != hipSuccess) {
     l->d_trip = nullptr;
     groove_ctl_link_destroy(l);
-    return fail(ctx, "groove_ctl_trip_create: hipMalloc failed");
+    return fail(ctx, who_s + "hipMalloc failed");
   }
   if (ctx_memcpy(ctx, l->d_trip, w.data(), w.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
     groove_ctl_link_destroy(l);
-    return fail(ctx, "groove_ctl_trip_create: the upload of the step table failed");
+    return fail(ctx, who_s + "the upload of the step table failed");
   }
-  ctx->links.push_back(l);
   *out = l;
   return 0;
 }
@@ -2911,6 +2956,7 @@ int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
   groove_ctx* ctx = l->ctx;
   groove_fx* fx = l->target;
   if (l->source != GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_trip_apply: not a trip link (an LFO or signal link is applied at a frame: groove_ctl_link_apply)");
+  if (l->on_bank) return bank_link_apply(l, "groove_ctl_trip_apply", at_units);
   if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_trip_apply: the target effect has been destroyed");
   GHIP(ctx, hipSetDevice(ctx->device));
   if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
@@ -2928,6 +2974,96 @@ int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+// ---- links onto a Welsh bank (dca-gain, dca-pan, filter-cutoff)
+// What both bank creates ask of their target.
+static int bank_link_check(groove_ctx* ctx, const char* who, groove_bank* b, uint32_t n_src, uint32_t control_index) {
+  const std::string w = std::string(who) + ": ";
+  if (std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, w + "the target is not a live bank of this context");
+  if (b->kind != BANK_WELSH) return fail(ctx, w + "only Welsh banks expose controls (FM and sampler banks have none)");
+  if (!ctl_bank_target_ok(control_index)) return fail(ctx, w + "unknown control index (a bank link reaches dca-gain, dca-pan or filter-cutoff)");
+  if (n_src != 1)
+    return fail(ctx, w + "n_src must be 1: the value is broadcast to every voice (a per-voice source would break the wave-uniform parameter records; per-voice changes keep groove_bank_set_param)");
+  return 0;
+}
+// The bank's side of a new link, before the link exists: the (gain, pan) shadow with the first gain or pan link.
+static int bank_link_prepare(groove_bank* b, const char* who, uint32_t control_index) {
+  groove_ctx* ctx = b->ctx;
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (control_index == GROOVE_CTL_WELSH_CUTOFF || b->d_dca) return 0;
+  if (hipMalloc(&b->d_dca, (size_t)CTL_DCA_WORDS * b->n * 4) != hipSuccess) {
+    b->d_dca = nullptr;
+    return fail(ctx, std::string(who) + ": hipMalloc failed");
+  }
+  return welsh_upload_dca(b); // from here on welsh_upload_params keeps it beside the records
+}
+// The bank re-planned for its count of cutoff links (welsh_plan.h welsh_flag_filter_f32): a control-plane step like groove_bank_set_param's,
+// which it repeats — the host's copy goes up again, the voices' state stays where it is.
+static int bank_replan(groove_bank* b) {
+  groove_ctx* ctx = b->ctx;
+  if (ctx_join(ctx)) return 1;
+  GHIP(ctx, ctx_wait(ctx));
+  b->ctx_touched = true;
+  return welsh_upload_params(b, false);
+}
+// The new link `l` onto `b`: listed with the bank; the first cutoff link takes WF_FILTER_F32 off the bank's records.
+static int bank_link_attach(groove_ctl_link* l, groove_bank* b) {
+  l->bank = b; l->on_bank = true;
+  if (l->control_index == GROOVE_CTL_WELSH_CUTOFF && b->cutoff_links++ == 0 && b->ctx->f32_filter && bank_replan(b)) {
+    groove_ctl_link_destroy(l);
+    return 1;
+  }
+  return 0;
+}
+int groove_ctl_bank_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_bank* target, uint32_t control_index,
+                                groove_ctl_link** out) {
+  const char* who = "groove_ctl_bank_link_create";
+  if (!ctx || !src || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
+  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_link_check_sources(ctx, who, src, n_src)) return 1;
+  if (bank_link_prepare(target, who, control_index)) return 1;
+  groove_ctl_link* l = nullptr;
+  if (ctl_link_make(ctx, who, src, n_src, nullptr, control_index, false, &l)) return 1;
+  if (bank_link_attach(l, target)) return 1;
+  *out = l;
+  return 0;
+}
+int groove_ctl_bank_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                                groove_bank* target, uint32_t control_index, groove_ctl_link** out) {
+  const char* who = "groove_ctl_bank_trip_create";
+  if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
+  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src)) return 1;
+  if (bank_link_prepare(target, who, control_index)) return 1;
+  groove_ctl_link* l = nullptr;
+  if (ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, control_index, &l)) return 1;
+  ctx->links.push_back(l);
+  if (bank_link_attach(l, target)) return 1;
+  *out = l;
+  return 0;
+}
+// groove_ctl_link_apply / groove_ctl_trip_apply on a bank link.  The bank's renders run on side streams: the ctx stream joins them by
+// events (no host wait), the kernel runs there, and every later render of the bank forks behind it (ctx_join: need_fork; ctx_touched
+// for the asynchronous render's own choice of what to wait for) — no render of the bank overlaps the write of its records.
+static int bank_link_apply(groove_ctl_link* l, const char* who, uint64_t at) {
+  groove_ctx* ctx = l->ctx;
+  groove_bank* b = l->bank;
+  if (!b || std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, std::string(who) + ": the target bank has been destroyed");
+  GHIP(ctx, hipSetDevice(ctx->device));
+  b->ctx_touched = true;
+  if (ctx_join(ctx)) return 1;
+  const CtlBank bank{b->d_params, b->plan.n_vwaves ? b->d_waves : nullptr, b->d_dca, b->n, b->plan.n_vwaves, l->control_index};
+  const dim3 grid(blocks_for(std::max<size_t>(b->n, b->plan.n_vwaves)));
+  if (l->source == GROOVE_CTL_SRC_TRIP) {
+    const size_t rows = (size_t)l->n_steps;
+    const double *begin = l->d_trip, *start = begin + rows + 1, *end = start + rows, *beats = end + rows;
+    const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
+    hipLaunchKernelGGL(ctl_trip_bank_apply_kernel, grid, dim3(kThreads), 0, ctx->stream, trip, at, bank);
+  } else {
+    const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + 2);
+    const CtlLanes lanes{l->d_lanes, l->d_lanes + 1, u, u + 1};
+    hipLaunchKernelGGL(ctl_bank_apply_kernel, grid, dim3(kThreads), 0, ctx->stream, l->source, lanes, at, l->d_value, l->d_captured, bank);
+  }
+  GHIP(ctx, hipGetLastError());
+  return 0;
+}
 int groove_ctl_link_reset(groove_ctl_link* l) {
   if (!l) return fail(nullptr, "groove_ctl_link_reset: link is NULL");
   groove_ctx* ctx = l->ctx;
@@ -2939,6 +3075,10 @@ int groove_ctl_link_reset(groove_ctl_link* l) {
 int groove_ctl_link_destroy(groove_ctl_link* l) {
   if (!l) return 0;
   groove_ctx* ctx = l->ctx;
+  // the last cutoff link off a live bank: its records may carry WF_FILTER_F32 again (bank_link_attach)
+  if (l->bank && l->control_index == GROOVE_CTL_WELSH_CUTOFF && std::find(ctx->banks.begin(), ctx->banks.end(), l->bank) != ctx->banks.end() &&
+      l->bank->cutoff_links && --l->bank->cutoff_links == 0 && ctx->f32_filter)
+    (void)bank_replan(l->bank);
   (void)hipStreamSynchronize(ctx->stream); // the link's kernels run there
   auto it = std::find(ctx->links.begin(), ctx->links.end(), l);
   if (it != ctx->links.end()) ctx->links.erase(it);

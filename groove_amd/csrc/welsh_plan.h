@@ -115,6 +115,17 @@ inline std::vector<uint32_t> welsh_patch_major_order(const std::vector<WelshPara
   return order;
 }
 
+// Which derived records carry WF_FILTER_F32.  The flag is a MEASURED property of the static cutoff (derive.h welsh_filter_f32_ok), and a
+// device link onto the bank's cutoff (groove_ctl_bank_link_create, GROOVE_CTL_WELSH_CUTOFF) moves that cutoff where the host cannot
+// measure: while the bank has `cutoff_links` > 0 of them no record carries the flag — the f64 recurrence is always safe.  Otherwise a
+// record carries it iff measured(record) says so (the bank's memo of welsh_filter_f32_ok).  `enabled`: the context's f32_filter knob.
+template <class Measured>
+void welsh_flag_filter_f32(std::vector<WelshParams>& ext, bool enabled, uint32_t cutoff_links, Measured&& measured) {
+  if (!enabled || cutoff_links) return; // (derive_welsh never sets the flag)
+  for (WelshParams& o : ext)
+    if (measured(o)) o.flags |= WF_FILTER_F32;
+}
+
 // The plan of a bank: `ext` / `cold_ext` are the derived records (WF_FILTER_F32 already decided) and cold values in the caller's
 // order, `perm` the lane order to keep them in (empty: the caller's).
 inline WelshPlan welsh_plan(const std::vector<WelshParams>& ext, const std::vector<WelshCold>& cold_ext, std::vector<uint32_t> perm) {

@@ -429,12 +429,15 @@ class ControlLink:
     """A controller device linked to one parameter of an Effect, resident on the device (groove_ctl_link): IsController.work
     once per block -> Controllable.control_set_param_by_index of the target, without a host wait.  `sources` is a ctypes array
     of abi_types.CtlSource, one per target lane or one for all.  derived=True makes it a FILTER link (groove_ctl_filter_link_create):
-    onto a filter's cutoff, q or passband-ripple, whose coefficients the link derives on the device."""
+    onto a filter's cutoff, q or passband-ripple, whose coefficients the link derives on the device.  A target that is an Instrument
+    makes it a BANK link (groove_ctl_bank_link_create): one source, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff."""
 
     def __init__(self, ctx, sources, target, control_index, derived=False):
         self.ctx, self.target, self.n_src, self.derived = ctx, target, len(sources), derived
         h = C.c_void_p()
         create = ctx.L.groove_ctl_filter_link_create if derived else ctx.L.groove_ctl_link_create
+        if isinstance(target, Instrument):
+            create = ctx.L.groove_ctl_bank_link_create
         _lib.check(create(ctx.h, sources, len(sources), target.h, control_index, C.byref(h)), ctx.h)
         self.h = h
 
@@ -460,7 +463,8 @@ class ControlTripLink:
     """A control trip linked to one parameter of an Effect, resident on the device (groove_ctl_trip_create): `lanes` is one list of
     steps (kind, start, end, beats) per source lane — one lane for every target lane, or one for all — and `start_beats` the lanes'
     start beats (a number: the same for all).  work(at_units) is IsController.work for the block that starts at that musical time,
-    abi_types.CTL_UNITS_PER_BEAT units per beat."""
+    abi_types.CTL_UNITS_PER_BEAT units per beat.  A target that is an Instrument makes it a BANK trip (groove_ctl_bank_trip_create):
+    one lane, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff."""
 
     def __init__(self, ctx, lanes, start_beats, target, control_index):
         self.ctx, self.target, self.n_src = ctx, target, len(lanes)
@@ -469,7 +473,8 @@ class ControlTripLink:
             start_beats = [start_beats] * len(lanes)
         starts = (C.c_double * len(lanes))(*start_beats)
         h = C.c_void_p()
-        _lib.check(ctx.L.groove_ctl_trip_create(ctx.h, steps, n_steps, starts, len(lanes), target.h, control_index, C.byref(h)), ctx.h)
+        create = ctx.L.groove_ctl_bank_trip_create if isinstance(target, Instrument) else ctx.L.groove_ctl_trip_create
+        _lib.check(create(ctx.h, steps, n_steps, starts, len(lanes), target.h, control_index, C.byref(h)), ctx.h)
         self.h = h
 
     def work(self, at_units):

@@ -1,12 +1,14 @@
 // groove-cli-hip — offline renderer, the GPU-path counterpart of the reference's `groove-cli`
 // (/root/reference/src/bin/groove-cli.rs:24-53 args, :56-158 main; gated at the reference commit).
 //
-//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--quiet] [--perf] [--debug] FILE...
+//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--quiet] [--perf] [--debug] FILE...
 //
 // --device-filter-links: `controls` onto a filter's cutoff, q or passband-ripple stay on the device (Orchestrator::set_filter_links_on_device),
 // a signal source's among them, which are dropped with a warning otherwise.
 // --device-trips: control trips onto effect parameters the library can reach stay on the device (Orchestrator::set_trips_on_device): no
 // host wait per automated block.
+// --device-instrument-controls: control trips and LFO `controls` onto a Welsh synth's dca-gain, dca-pan or filter-cutoff stay on the device
+// (Orchestrator::set_instrument_controls_on_device): no re-plan and re-upload of the synth's bank per automated block.
 //
 // For each project file: SongSettings::new_from_project_file → instantiate → update_sample_rate(44100)
 // → run_performance(buffer) → (with --wav) send_performance_to_file(<input with .json5/.json → .wav>).
@@ -29,7 +31,7 @@ static std::string wav_name(const std::string& in) {
 }
 
 int main(int argc, char** argv) {
-  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false;
+  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false, instrument_controls = false;
   int device = 0;
   std::string assets = "assets";
   std::vector<std::string> inputs;
@@ -42,11 +44,12 @@ int main(int argc, char** argv) {
     else if (a == "--synthetic-kit") synthetic = true;
     else if (a == "--device-filter-links") filter_links = true;
     else if (a == "--device-trips") device_trips = true;
+    else if (a == "--device-instrument-controls") instrument_controls = true;
     else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--version" || a == "-v") { std::printf("groove-cli-hip 0.1 (MI355X render path)\n"); return 0; }
     else if (a == "--help" || a == "-h") {
-      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--quiet] [--perf] [--debug] FILE...\n");
+      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--quiet] [--perf] [--debug] FILE...\n");
       return 0;
     } else inputs.push_back(a);
   }
@@ -65,6 +68,7 @@ int main(int argc, char** argv) {
     if (!o.ctx()) { std::fprintf(stderr, "no HIP device: %s (this renderer has no CPU path)\n", o.last_error().c_str()); return 1; }
     o.set_filter_links_on_device(filter_links);
     o.set_trips_on_device(device_trips);
+    o.set_instrument_controls_on_device(instrument_controls);
     if (instantiate(o, desc, assets, synthetic)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (!quiet) std::printf("Performing to queue %s\n", in.c_str());
     const auto t0 = std::chrono::steady_clock::now();

@@ -112,7 +112,7 @@ ControlSource::~ControlSource() {
 }
 void ControlSource::work_controls(Orchestrator& o, uint64_t at_frame) {
   for (const Link& l : links_) {
-    if (l.dev) o.control_link(l.dev, at_frame);
+    if (l.dev) o.control_link(l.dev, at_frame, false, l.instrument);
     else o.control_effect(l.target, l.index, host_value01(at_frame, o.sample_rate()));
   }
 }
@@ -179,9 +179,10 @@ uint64_t ControlTrip::end_units_() const {
   for (auto& s : steps_) b += s.beats;
   return MusicalTime::from_beats(b).units;
 }
-void ControlTrip::set_device_link(groove_ctl_link* link) {
+void ControlTrip::set_device_link(groove_ctl_link* link, bool on_instrument) {
   if (dev_) groove_ctl_link_destroy(dev_);
   dev_ = link;
+  dev_instrument_ = link && on_instrument;
   last_step_ = -1;
 }
 void ControlTrip::work(uint64_t start_units, uint64_t end_units, std::vector<MidiEvent>&, Orchestrator& o) {
@@ -193,7 +194,7 @@ void ControlTrip::work(uint64_t start_units, uint64_t end_units, std::vector<Mid
     if (dev_ && now >= b && now < b + s.beats) {
       // the link's kernel finds the step again and evaluates it; a FLAT step it has already been given holds nothing new (the host trip's
       // "sent when it changes", for the one case that is known without evaluating anything)
-      if (s.kind != ControlStep::FLAT || i != last_step_) o.control_link(dev_, start_units, true);
+      if (s.kind != ControlStep::FLAT || i != last_step_) o.control_link(dev_, start_units, true, dev_instrument_);
       last_step_ = i;
       return;
     }
@@ -424,17 +425,23 @@ void Orchestrator::place_trips() {
   for (auto& n : nodes_)
     if (n.entity && n.entity->control_trip()) trips.push_back(n.entity->control_trip());
   for (ControlTrip* t : trips) t->set_device_link(nullptr); // decided anew for every performance: the switch and the links may have changed
-  if (!trips_on_device_) return;
+  if (!trips_on_device_ && !instrument_controls_on_device_) return;
   auto fx_of = [&](Uid target) -> groove_fx* {
     Entity* e = get(target);
     return e && e->is_effect() ? static_cast<Effect*>(e)->library_fx() : nullptr;
   };
+  auto bank_of = [&](Uid target) -> groove_bank* {
+    Entity* e = get(target);
+    return e && e->is_instrument() ? static_cast<Instrument*>(e)->fused_bank() : nullptr;
+  };
   auto reachable = [&](const ControlTrip* t) {
-    if (!fx_of(t->target()) || t->steps().empty()) return false;
+    if (t->steps().empty()) return false;
+    if (bank_of(t->target())) return instrument_controls_on_device_ && bank_control_device_linkable((int)t->control_index());
+    if (!trips_on_device_ || !fx_of(t->target())) return false;
     const uint32_t kind = static_cast<FxEffect*>(get(t->target()))->kind();
     return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index());
   };
-  // the effects that ANY control reaches through the host: a trip the library cannot take, a `controls` link without a device link
+  // the effects and instruments that ANY control reaches through the host: a trip the library cannot take, a `controls` link without a device link
   std::vector<char> host_path(nodes_.size(), 0);
   for (ControlTrip* t : trips)
     if (t->target() < nodes_.size() && !reachable(t)) host_path[t->target()] = 1;
@@ -448,14 +455,16 @@ void Orchestrator::place_trips() {
     for (const ControlStep& s : t->steps()) steps.push_back({(uint32_t)s.kind, s.start, s.end, s.beats});
     const double start = t->start_beat();
     groove_ctl_link* link = nullptr;
-    if (groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
-      // the library has the last word (a step it refuses: zero beats, a Triggered step): this effect's trips all stay on the host
+    groove_bank* bank = bank_of(t->target());
+    if (bank ? groove_ctl_bank_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, bank, t->control_index(), &link)
+             : groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
+      // the library has the last word (a step it refuses: zero beats, a Triggered step; a bank that is no Welsh bank): this target's trips all stay on the host
       host_path[t->target()] = 1;
       for (ControlTrip* u : trips)
         if (u->target() == t->target()) u->set_device_link(nullptr);
       continue;
     }
-    t->set_device_link(link);
+    t->set_device_link(link, bank != nullptr);
   }
 }
 int Orchestrator::link_control(Uid source, Uid target, const std::string& param) {
@@ -480,6 +489,15 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
     src->add_link({link, target, (uint32_t)idx});
     return 0;
   }
+  groove_bank* bank = te->is_instrument() ? static_cast<Instrument*>(te)->fused_bank() : nullptr;
+  if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(idx)) {
+    groove_ctl_link* link = nullptr;
+    if (!groove_ctl_bank_link_create(ctx_, &desc, 1, bank, (uint32_t)idx, &link)) {
+      src->add_link({link, target, (uint32_t)idx, true});
+      return 0;
+    }
+    // (the library refuses: a bank that is no Welsh bank, a noise LFO — the host path below, with its own checks)
+  }
   if (desc.source == GROOVE_CTL_SRC_SIGNAL) {
     err_ = "link_control: a signal source onto '" + param + "' would need a download per block (the host derives that parameter's device form); dropped";
     return 2;
@@ -488,8 +506,8 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
   src->add_link({nullptr, target, (uint32_t)idx});
   return 0;
 }
-int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units) {
-  if (deferring_) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
+int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units, bool on_instrument) {
+  if (deferring_ && !on_instrument) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
   if (trip_units ? groove_ctl_trip_apply(link, at) : groove_ctl_link_apply(link, at)) return fail(groove_last_error(ctx_));
   return 0;
 }
@@ -790,6 +808,7 @@ void gh_set_render_ahead(void* h, int mode) { ((Orchestrator*)h)->set_render_ahe
 void gh_set_fused_direct(void* h, int on) { ((Orchestrator*)h)->set_fused_direct(on != 0); }
 void gh_set_filter_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_filter_links_on_device(on != 0); }
 void gh_set_trips_on_device(void* h, int on) { ((Orchestrator*)h)->set_trips_on_device(on != 0); }
+void gh_set_instrument_controls_on_device(void* h, int on) { ((Orchestrator*)h)->set_instrument_controls_on_device(on != 0); }
 // 1: the trip has been device-resident since the last skip_to_start (a run's start); 0: it goes through the host (or is no trip)
 int gh_control_trip_on_device(void* h, int uid) {
   Entity* e = ((Orchestrator*)h)->get((Uid)uid);

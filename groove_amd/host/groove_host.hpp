@@ -89,6 +89,11 @@ inline int bank_control_index_for_name(const std::string& name) {
   for (auto& t : table) if (name == t.first) return t.second;
   return -1;
 }
+// The controls of a Welsh synth a BANK link reaches (groove_ctl_bank_link_create / groove_ctl_bank_trip_create, which have the last word: the
+// bank has to be a Welsh one).
+inline bool bank_control_device_linkable(int index) {
+  return index == GROOVE_CTL_WELSH_DCA_GAIN || index == GROOVE_CTL_WELSH_DCA_PAN || index == GROOVE_CTL_WELSH_CUTOFF;
+}
 // Can a control link onto this parameter of this kind of effect stay on the device (groove_ctl_link_create: the parameters whose device
 // form IS the value, on the kind whose kernels read them)?  (A filter's cutoff, q and passband-ripple can too, through a filter link, where
 // the orchestrator has been asked to: Orchestrator::set_filter_links_on_device, fx_control_device_derived below.)
@@ -287,7 +292,8 @@ class ControlTrip : public Controller {
   double start_beat() const { return start_; }
   const std::vector<ControlStep>& steps() const { return steps_; }
   bool on_device() const { return dev_ != nullptr; }
-  void set_device_link(groove_ctl_link* link); // takes ownership; destroys the link it had
+  // takes ownership; destroys the link it had.  on_instrument: a bank link — its applies are never held back (Orchestrator::control_link)
+  void set_device_link(groove_ctl_link* link, bool on_instrument = false);
   void work(uint64_t start_units, uint64_t end_units, std::vector<MidiEvent>& out, Orchestrator& o) override;
   bool is_finished(uint64_t end_units) const override { return end_units >= end_units_(); }
   uint64_t end_units() const override { return end_units_(); }
@@ -300,6 +306,7 @@ class ControlTrip : public Controller {
   std::vector<ControlStep> steps_;
   double last_sent_ = -1.0;
   groove_ctl_link* dev_ = nullptr; // device-resident: the trip link
+  bool dev_instrument_ = false;    // device-resident: the link's target is an instrument's bank
   int last_step_ = -1;             // device-resident: the step of the last apply (a FLAT step is applied once)
 };
 
@@ -311,7 +318,7 @@ class ControlTrip : public Controller {
 class ControlSource {
  public:
   virtual ~ControlSource();
-  struct Link { groove_ctl_link* dev; Uid target; uint32_t index; }; // dev == nullptr: through Orchestrator::control_effect
+  struct Link { groove_ctl_link* dev; Uid target; uint32_t index; bool instrument = false; }; // dev == nullptr: through Orchestrator::control_effect; instrument: dev is a bank link
   virtual groove_ctl_source source_desc() const = 0;
   void add_link(const Link& l) { links_.push_back(l); }
   const std::vector<Link>& link_list() const { return links_; }
@@ -410,7 +417,9 @@ class Orchestrator {
   // A device-resident link's value for the block at `at`: applied now, or — like control_effect — held back while the controllers
   // are run one block ahead of the effects.  `at` is the block's first frame (an LFO or signal link: groove_ctl_link_apply) or, for a
   // trip link, its start in musical-time units (groove_ctl_trip_apply).
-  int control_link(groove_ctl_link* link, uint64_t at, bool trip_units = false);
+  // A link onto an INSTRUMENT (a bank link) is applied at once even then, as control_effect's instrument branch is: the instruments are
+  // the block being sequenced.
+  int control_link(groove_ctl_link* link, uint64_t at, bool trip_units = false, bool on_instrument = false);
   // ControlTrips onto effect parameters the library can reach (groove_ctl_trip_create) stay on the device: no groove_fx_set_param, and so
   // no host wait, per automated block.  Decided for all trips at once when a performance starts (skip_to_start): a trip is device-resident
   // iff the switch is on, its target is an effect, the library accepts the parameter for that kind, and EVERY other control onto the same
@@ -418,6 +427,17 @@ class Orchestrator {
   // parameter the device trip owns.  Everything else (instruments, wet-dry-mix) takes the host path unchanged.  Off by default.
   void set_trips_on_device(bool on) { trips_on_device_ = on; }
   bool trips_on_device() const { return trips_on_device_; }
+  // Controls onto a Welsh synth's dca-gain / gain, dca-pan / pan or filter-cutoff / cutoff stay on the device (groove_ctl_bank_trip_create,
+  // groove_ctl_bank_link_create): no groove_bank_set_param — a re-derivation, a re-plan and a re-upload of the bank, with their host waits —
+  // per automated block.  Off by default and independent of set_trips_on_device.  Trips are placed when a performance starts
+  // (skip_to_start), by the effects' rule per instrument: if ANY control reaches the instrument through the host — a parameter or a bank
+  // the library refuses, an LFO link without a device link, a create that fails — ALL its trips stay on the host, because a host
+  // set_param re-uploads the host's copy over the device's value.  LFO `controls` links are made by link_control, so the switch has to be
+  // set before the project's controls are linked.  A signal-passthrough source onto an instrument stays dropped (status 2) either way:
+  // in the render-ahead walk the instruments of block b + 1 render before block b's effects have captured anything, so the reference's
+  // "value captured in the previous tick" cannot be honoured there (the library call takes signal sources; the host layer does not use it).
+  void set_instrument_controls_on_device(bool on) { instrument_controls_on_device_ = on; }
+  bool instrument_controls_on_device() const { return instrument_controls_on_device_; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -462,6 +482,7 @@ class Orchestrator {
   bool fused_direct_ = true;
   bool filter_links_on_device_ = false;
   bool trips_on_device_ = false;
+  bool instrument_controls_on_device_ = false;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block

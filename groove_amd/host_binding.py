@@ -28,6 +28,7 @@ def load():
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
         "gh_set_trips_on_device": (None, [vp, i]), "gh_control_trip_on_device": (i, [vp, i]),
+        "gh_set_instrument_controls_on_device": (None, [vp, i]),
         "gh_debug_info": (i, [vp, C.c_char_p, C.c_size_t]), "gh_connect_midi_downstream": (i, [vp, i, i]),
         "gh_add_timer": (i, [vp, d]), "gh_add_sequencer": (i, [vp]),
         "gh_sequencer_insert": (i, [vp, i, i, i, d, d]), "gh_sequencer_set_end": (i, [vp, i, d]),
@@ -99,6 +100,13 @@ class Orchestrator:
         """Control trips onto effect parameters the library can reach stay on the device (no host wait per automated block); decided for
         all trips when a run starts — control_trip_on_device(uid) says how it went.  Off by default."""
         self.L.gh_set_trips_on_device(self.h, 1 if on else 0)
+
+    def set_instrument_controls_on_device(self, on):
+        """Control trips and LFO `controls` links onto a Welsh synth's dca-gain, dca-pan or filter-cutoff stay on the device (no re-upload
+        of the synth's bank, and no host wait, per automated block).  Trips are decided when a run starts — control_trip_on_device(uid)
+        says how it went — LFO links when they are made, so set it before link_control.  Off by default; independent of
+        set_trips_on_device."""
+        self.L.gh_set_instrument_controls_on_device(self.h, 1 if on else 0)
 
     def control_trip_on_device(self, uid):
         """1: the trip has been device-resident since the last run started; 0: it goes through the host."""

@@ -97,6 +97,8 @@ SYMBOLS = {
     "groove_ctl_link_apply": (_i, [_vp, C.c_uint64]),
     "groove_ctl_trip_create": (_i, [_vp, C.POINTER(T.CtlStep), _u32, C.POINTER(C.c_double), _u32, _vp, _u32, _vpp]),
     "groove_ctl_trip_apply": (_i, [_vp, C.c_uint64]),
+    "groove_ctl_bank_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),
+    "groove_ctl_bank_trip_create": (_i, [_vp, C.POINTER(T.CtlStep), _u32, C.POINTER(C.c_double), _u32, _vp, _u32, _vpp]),
     "groove_ctl_link_reset": (_i, [_vp]),
     "groove_ctl_link_destroy": (_i, [_vp]),
     "groove_mix": (_i, [_vp, _vpp, _u32, _u32, _vp, _i]),

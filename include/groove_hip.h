@@ -365,6 +365,37 @@ int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32
  * re-sends only when its value changes, an apply inside a step ALWAYS writes, so it also restores a linked parameter that a
  * groove_fx_set_param(s) on the target has overwritten since. */
 int groove_ctl_trip_apply(groove_ctl_link* link, uint64_t at_units);
+/* A BANK link: a controller linked to a Welsh synth's dca-gain, dca-pan or filter-cutoff — Controllable on the instrument, which
+ * groove_bank_set_param(bank, GROOVE_ALL_VOICES, ...) serves by re-deriving, re-planning and re-uploading the whole bank with host
+ * waits around each copy.  The link's apply is one small kernel on the ctx stream instead: it computes the control value, turns it
+ * into the parameter by groove_bank_set_param's law (gain: clamp01(v); pan: clamp01(v) * 2 - 1; cutoff: 25 * 800^clamp01(v) Hz, each
+ * rounded to the float groove_welsh_params holds) and writes the words the voice kernels read at the start of a block — gl and gr
+ * (the pan law of the bank's per-voice gain and pan, csrc/ctl_core.h pan_gains) or cutoff_hz — into the per-lane parameter array AND
+ * the per-virtual-wave copies.  No host wait, no copy.
+ *   src[1] / steps[1][n_steps], start_beat[1]: ONE source, broadcast to every voice (what GROOVE_ALL_VOICES does).  n_src != 1 is
+ *   refused: per-voice values would break the wave-uniform parameter records; per-voice changes keep groove_bank_set_param.
+ *   control_index: GROOVE_CTL_WELSH_DCA_GAIN, _DCA_PAN or _CUTOFF on a Welsh bank.  Refused: any other index, FM and sampler banks,
+ *   a bank that is not live, and whatever groove_ctl_link_create / groove_ctl_trip_create refuse of their sources and steps.
+ * Gain and pan share two words, so the bank gets a per-voice (gain, pan) shadow on the device with its first gain or pan link;
+ * groove_bank_set_param, a sample-rate change and a reset refresh it from the host's copy.  The staleness rule of the effect links
+ * holds unchanged: a link does not update the host's copy, a later groove_bank_set_param re-uploads it and overwrites the linked
+ * parameter until the link's next apply (a trip's apply inside a step always writes), and two links onto one bank (gain and pan) see
+ * each other's last value in the order of their applies.
+ * Cutoff and the fp32 filter: whether a patch's filter may run in fp32 is MEASURED on the host for its static cutoff, and a link moves
+ * that cutoff where the host cannot measure.  While a bank has a live cutoff link its voices run the f64 recurrence (always safe);
+ * the bank is re-planned — like a groove_bank_set_param, host's copy re-uploaded — when the first such link is created and when the
+ * last one is destroyed.  A cutoff link onto a patch whose filter is retuned by its envelope or LFO is accepted and inaudible, as the
+ * host path is: those bodies do not read the static cutoff.
+ * Ordering: the apply runs behind every render of the bank submitted so far and ahead of every later one, joined and forked by
+ * events; it is a between-blocks change like a note event.  A signal link's capture block has one lane.  (The compiled host layer
+ * does not make signal links onto instruments: in its render-ahead walk the instruments of block b + 1 render before block b's
+ * effects have captured anything, so "the value captured in the previous tick" does not exist there.)
+ * The link returned is an ordinary one: capture, apply / trip apply, reset and destroy under their own rules.  groove_bank_destroy
+ * leaves it without a target: its next apply is an error. */
+int groove_ctl_bank_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_bank* target, uint32_t control_index,
+                                groove_ctl_link** out);
+int groove_ctl_bank_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                                groove_bank* target, uint32_t control_index, groove_ctl_link** out);
 /* Resets::reset (Orchestrator::skip_to_start, orchestrator.rs:971-983): a signal link forgets what it captured. */
 int groove_ctl_link_reset(groove_ctl_link* link);
 /* Orchestrator::unlink_control (orchestrator.rs:1296-1320).  groove_shutdown frees the links that are still alive. */
