@@ -100,7 +100,9 @@ GROOVE_HD double ctl_trip_value(uint32_t kind, double start, double end, double 
 // ------------------------------------------------------------------ targets
 // groove_fx_set_param's laws where the device form IS the value.  The others are derived on the host in f64 (cutoff, q,
 // passband-ripple -> coefficients; a FILTER link derives them on the device instead, below) or choose a kernel path there
-// (wet-dry-mix -> all_wet): a plain link cannot reach them.
+// (wet-dry-mix -> all_wet): a plain link cannot reach them.  wet-dry-mix has creates of its own (groove_ctl_wet_link_create /
+// groove_ctl_wet_trip_create): its device form is the value too (ctl_target_float / ctl_target_float_f64 below), and the one host
+// decision that hangs on it, a reverb's form, is made from the reverb's count of live wet links.
 GROOVE_HD bool ctl_target_linkable(uint32_t control_index) {
   switch (control_index) {
     case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_BITS: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD: return true;

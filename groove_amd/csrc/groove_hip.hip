@@ -163,7 +163,8 @@ struct groove_fx {
   size_t ring_rows = 0;
   // uniform geometry
   uint32_t N = 0, w = 0, voices = 1, spacing = 0;
-  bool all_wet = true; // every lane has wet == 1 (enables the split reverb path)
+  bool all_wet = true; // every lane of the HOST's copy has wet == 1 (enables the split reverb path)
+  uint32_t wet_links = 0; // live wet links (groove_ctl_wet_link_create / groove_ctl_wet_trip_create): above zero the device's wet values are not the host's, so a reverb counts as not all wet (fx_needs_dry)
   ReverbGeom geo{};
   // reverb, direct all-pass form (kernels.h): second copies of the two all-pass rings (read one, write the other, swap)
   // and a staging block for the comb sum, allocated at first use
@@ -256,6 +257,7 @@ struct groove_ctx {
   TpPrev deferred_ap;
   hipEvent_t ev_ap_run = nullptr, ev_ap_x = nullptr;
   bool seq_allpass = false;             // GROOVE_FX_SEQ_ALLPASS=1: the sequential all-pass kernel (A/B and bit-identity tests)
+  bool fx_wet_reverb_run = false;       // groove_set_fx_wet_reverb_run / GROOVE_FX_WET_REVERB_RUN=1: a partly wet reverb keeps the fused run (fx_form_of)
   bool chunked_allpass = false;         // GROOVE_FX_CHUNKED_ALLPASS=1: the chunk-parallel all-pass kernel instead of the direct one
   uint32_t sr = GROOVE_DEFAULT_SAMPLE_RATE;
   // Blocking waits (groove_synchronize and every call that hands data to the host) poll the stream with a deadline
@@ -1157,6 +1159,7 @@ static int init_impl(int device_ordinal, const uint8_t* comm_id, int rank, int w
   if (const char* e = std::getenv("GROOVE_FM_TP_VPW4_MIN_VOICES")) ctx->fm_tp_vpw4_min_voices = (uint32_t)std::strtoul(e, nullptr, 10);
   if (const char* e = std::getenv("GROOVE_BIND_EVENTS")) ctx->bind_events = std::atoi(e) != 0;
   if (const char* e = std::getenv("GROOVE_FX_CHUNKED_ALLPASS")) ctx->chunked_allpass = e[0] == '1';
+  if (const char* e = std::getenv("GROOVE_FX_WET_REVERB_RUN")) ctx->fx_wet_reverb_run = e[0] == '1';
   if (const char* e = std::getenv("GROOVE_TP_MAX_VOICES")) ctx->tp_max_voices = (uint32_t)std::strtoul(e, nullptr, 10);
   if (const char* e = std::getenv("GROOVE_SPLIT_MAX_WAVES")) ctx->split_max_waves = (uint32_t)std::strtoul(e, nullptr, 10);   // (A/B runs: tools/ab_env.sh)
   if (const char* e = std::getenv("GROOVE_F32_FILTER")) ctx->f32_filter = e[0] != '0'; // (A/B and the bit-identity tests between kernel forms)
@@ -1326,6 +1329,14 @@ int groove_set_fx_allpass_stream(groove_ctx* ctx, int on) {
   return 0;
 }
 int groove_fx_allpass_stream(groove_ctx* ctx) { return ctx ? (ctx->fx_ap_stream >= 0 ? 1 : 0) : 0; }
+// Host-side only: the form is decided per launch (fx_form_of), and a reverb's lines mean the same to every form (the all-pass rings'
+// live copies are geo.base[4..5] whichever kernel wrote them last), so nothing in flight has to finish first.
+int groove_set_fx_wet_reverb_run(groove_ctx* ctx, int on) {
+  if (!ctx) return fail(nullptr, "groove_set_fx_wet_reverb_run: ctx is NULL");
+  ctx->fx_wet_reverb_run = on != 0;
+  return 0;
+}
+int groove_fx_wet_reverb_run(groove_ctx* ctx) { return ctx ? (ctx->fx_wet_reverb_run ? 1 : 0) : 0; }
 int groove_set_split_max_waves(groove_ctx* ctx, uint32_t waves) {
   if (!ctx) return fail(nullptr, "groove_set_split_max_waves: ctx is NULL");
   if (ctx_join(ctx)) return 1;
@@ -2345,6 +2356,10 @@ static const char* const kFxFormNames[(size_t)FxForm::Count] = {
 // `last_on_ctx`: the launch is the last of its chain and goes to the ctx stream (only such a launch may leave for the all-pass
 // stream).  The element-wise kinds are always stages of a fused run (kernels.h, fx_run_kernel); a delay line is one when it is
 // at least a block long (no feedback inside the block).
+// A reverb whose output needs its input again: a lane of the host's copy is below wet 1, or a wet link is alive (the device's values
+// are then the link's, whatever the host's copy says).  Such a reverb walks the frames serially (fx_reverb_kernel) unless
+// groove_set_fx_wet_reverb_run is on; then it takes the run's forms with the DRY instantiations of their kernels (kernels.h).
+static bool fx_needs_dry(const groove_fx* fx) { return !fx->all_wet || fx->wet_links > 0; }
 static FxForm fx_form_of(const groove_fx* fx, const groove_block* io, uint32_t frames, bool last_on_ctx) {
   const groove_ctx* ctx = fx->ctx;
   const size_t n = fx->n;
@@ -2372,9 +2387,11 @@ static FxForm fx_form_of(const groove_fx* fx, const groove_block* io, uint32_t f
       uint32_t shortest_comb = fx->geo.N[0];
       for (int i = 1; i < 4; ++i) shortest_comb = std::min(shortest_comb, fx->geo.N[i]);
       const uint32_t shortest_ap = std::min(fx->geo.N[4], fx->geo.N[5]);
-      if (!(fx->all_wet && shortest_comb >= frames && shortest_ap >= 32)) return std::min(shortest_comb, shortest_ap) >= 8 ? FxForm::Reverb8 : FxForm::Reverb1;
+      if (!((!fx_needs_dry(fx) || ctx->fx_wet_reverb_run) && shortest_comb >= frames && shortest_ap >= 32)) return std::min(shortest_comb, shortest_ap) >= 8 ? FxForm::Reverb8 : FxForm::Reverb1;
       // the direct all-pass form unrolls at most 8 hops per frame, and wants the comb sum in a staging block of the block's capacity
       const bool direct = !ctx->seq_allpass && !ctx->chunked_allpass && frames <= 8 * shortest_ap && (size_t)2 * io->cap * n * 4 <= ((size_t)1 << 30);
+      // (the other forms keep the dry signal in a staging block of the same size)
+      if (!direct && fx_needs_dry(fx) && (size_t)2 * io->cap * n * 4 > ((size_t)1 << 30)) return std::min(shortest_comb, shortest_ap) >= 8 ? FxForm::Reverb8 : FxForm::Reverb1;
       if (direct) return last_on_ctx && ctx->fx_ap_stream >= 0 && io->ev_free ? FxForm::RunDirectAp : FxForm::RunDirect;
       return ctx->seq_allpass ? FxForm::RunSeq : FxForm::RunChunked;
     }
@@ -2409,7 +2426,15 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
   a.src = io->d; a.src_chs = chs;
   a.dst = io->d; a.dst_chs = chs;
   groove_fx* rv = run[count - 1]->kind == GROOVE_FX_REVERB ? run[count - 1] : nullptr;
-  bool direct = false, on_ap = false, seq = false;
+  bool direct = false, on_ap = false, seq = false, dry = false;
+  auto tmp_block = [&]() -> int { // the reverb's staging block, of the block's capacity
+    if (rv->tmp_cap >= io->cap) return 0;
+    GHIP(ctx, wait_deadline(ctx, st, nullptr, "effect staging block"));
+    if (rv->d_tmp) { GHIP(ctx, hipFree(rv->d_tmp)); rv->d_tmp = nullptr; rv->tmp_cap = 0; }
+    GHIP(ctx, hipMalloc(&rv->d_tmp, (size_t)2 * io->cap * n * 4));
+    rv->tmp_cap = io->cap;
+    return 0;
+  };
   if (rv) {
     a.geo = rv->geo;
     // the direct all-pass form wants the comb sum in a staging block (it reads other frames than the one it writes)
@@ -2428,13 +2453,16 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
       }
       a.dst = io->d_stage; a.dst_chs = (size_t)io->stage_cap * n;
     } else if (direct) {
-      if (rv->tmp_cap < io->cap) {
-        GHIP(ctx, wait_deadline(ctx, st, nullptr, "effect staging block"));
-        if (rv->d_tmp) { GHIP(ctx, hipFree(rv->d_tmp)); rv->d_tmp = nullptr; rv->tmp_cap = 0; }
-        GHIP(ctx, hipMalloc(&rv->d_tmp, (size_t)2 * io->cap * n * 4));
-        rv->tmp_cap = io->cap;
-      }
+      if (tmp_block()) return 1;
       a.dst = rv->d_tmp; a.dst_chs = (size_t)rv->tmp_cap * n;
+    }
+    // the reverb's input, for the wet-dry mix behind the all-passes (kernels.h, fx_wet_mix): in the block itself under the direct
+    // forms, in the reverb's staging block otherwise (the comb sum is in the block then)
+    dry = fx_needs_dry(rv);
+    if (dry && direct) { a.dry = io->d; a.dry_chs = chs; }
+    else if (dry) {
+      if (tmp_block()) return 1;
+      a.dry = rv->d_tmp; a.dry_chs = (size_t)rv->tmp_cap * n;
     }
   }
   const dim3 blk(kThreads);
@@ -2463,8 +2491,12 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
   }
   a.rows = (rv && direct) ? nullptr : rows;
   if (rv && !direct) rows = nullptr; // the sequential / chunked all-pass kernels run last and leave none
-  if (V == 4) hipLaunchKernelGGL(fx_run_kernel<4>, dim3(2 * wg_per_ch, frames), blk, 0, st, a);
-  else hipLaunchKernelGGL(fx_run_kernel<1>, dim3(2 * wg_per_ch, frames), blk, 0, st, a);
+  const dim3 run_grid(2 * wg_per_ch, frames);
+  if (dry) { // (the all-wet launches keep the instantiations without the dry store)
+    if (V == 4) hipLaunchKernelGGL((fx_run_kernel<4, true>), run_grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((fx_run_kernel<1, true>), run_grid, blk, 0, st, a);
+  } else if (V == 4) hipLaunchKernelGGL((fx_run_kernel<4, false>), run_grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((fx_run_kernel<1, false>), run_grid, blk, 0, st, a);
   if (rv) {
     const ReverbGeom& g = rv->geo;
     if (direct) {
@@ -2478,7 +2510,15 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
       }
       d.n = n; d.frames = frames;
       d.rows = rows; d.wg_per_ch = wg_per_ch;
-      const uint32_t grid_rows = std::max(frames, std::max(g.N[4], g.N[5]));
+      d.wet = rv->d_wet;
+      const dim3 ap_grid(2 * wg_per_ch, std::max(frames, std::max(g.N[4], g.N[5])));
+      auto launch_direct = [&](hipStream_t on) {
+        if (dry) {
+          if (V == 4) hipLaunchKernelGGL((fx_reverb_allpass_direct_kernel<4, true>), ap_grid, blk, 0, on, d);
+          else hipLaunchKernelGGL((fx_reverb_allpass_direct_kernel<1, true>), ap_grid, blk, 0, on, d);
+        } else if (V == 4) hipLaunchKernelGGL((fx_reverb_allpass_direct_kernel<4, false>), ap_grid, blk, 0, on, d);
+        else hipLaunchKernelGGL((fx_reverb_allpass_direct_kernel<1, false>), ap_grid, blk, 0, on, d);
+      };
       hipStream_t ast = st;
       if (on_ap) {
         const int k = ctx->fx_ap_stream;
@@ -2490,22 +2530,22 @@ static int fx_launch_run(groove_ctx* ctx, groove_fx* const* run, uint32_t count,
           d.prev = ctx->deferred_ap;
           ctx->deferred_ap = TpPrev{};
         }
-        if (V == 4) hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<4>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
-        else hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<1>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
+        launch_direct(ast);
         GHIP(ctx, hipEventRecord(io->ev_ready[k], ast)); // the block is ready when that kernel is
         io->ready_mask |= 1u << k;
         ctx->side_busy[k] = true;
         rv->ap_busy = true;
       } else {
-        if (V == 4) hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<4>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
-        else hipLaunchKernelGGL(fx_reverb_allpass_direct_kernel<1>, dim3(2 * wg_per_ch, grid_rows), blk, 0, ast, d);
+        launch_direct(ast);
       }
       for (int i = 0; i < 2; ++i) std::swap(rv->geo.base[4 + i], rv->ap_alt[i]);
     } else if (seq) {
-      hipLaunchKernelGGL(fx_reverb_allpass_kernel<32>, dim3(blocks_for(2 * (size_t)n)), blk, 0, st, io->d, n, frames, chs, rv->d_ring, g);
+      if (dry) hipLaunchKernelGGL((fx_reverb_allpass_kernel<32, true>), dim3(blocks_for(2 * (size_t)n)), blk, 0, st, io->d, n, frames, chs, rv->d_ring, g, a.dry, a.dry_chs, rv->d_wet);
+      else hipLaunchKernelGGL((fx_reverb_allpass_kernel<32, false>), dim3(blocks_for(2 * (size_t)n)), blk, 0, st, io->d, n, frames, chs, rv->d_ring, g, (const float*)nullptr, (size_t)0, (const float*)nullptr);
     } else { // chunks of one line length, parallel inside (kernels.h)
       const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(64, 2 * n / 512));
-      hipLaunchKernelGGL(fx_reverb_allpass_chunked_kernel, dim3((2 * n + T - 1) / T), dim3(kAllpassThreads), 0, st, io->d, n, frames, chs, rv->d_ring, g, T);
+      if (dry) hipLaunchKernelGGL(fx_reverb_allpass_chunked_kernel<true>, dim3((2 * n + T - 1) / T), dim3(kAllpassThreads), 0, st, io->d, n, frames, chs, rv->d_ring, g, T, a.dry, a.dry_chs, rv->d_wet);
+      else hipLaunchKernelGGL(fx_reverb_allpass_chunked_kernel<false>, dim3((2 * n + T - 1) / T), dim3(kAllpassThreads), 0, st, io->d, n, frames, chs, rv->d_ring, g, T, (const float*)nullptr, (size_t)0, (const float*)nullptr);
     }
   }
   for (uint32_t s = 0; s < count; ++s) fx_advance(run[s], frames);
@@ -2820,6 +2860,42 @@ int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src,
   }
   return ctl_link_make(ctx, who, src, n_src, target, control_index, true, out);
 }
+// ---- links onto wet-dry-mix
+// Every effect kernel reads d_wet[lane] at launch and takes `wm < 1` per lane; the one HOST decision that hangs on the value is a
+// reverb's form, and a reverb counts its live wet links for that (fx_needs_dry).  The law is groove_fx_set_param's (float)clamp01(v):
+// ctl_target_float / ctl_target_float_f64, which the existing apply kernels store — into d_wet instead of d_fa (ctl_float_words).
+// The applies' fx_ap_settle orders the store behind a direct all-pass kernel that is still reading d_wet on the all-pass stream
+// (events between streams: no host wait).
+static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src);
+static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                         uint32_t control_index, groove_ctl_link** out);
+static int wet_link_check_target(groove_ctx* ctx, const char* who, groove_fx* target) {
+  if (target->kind == GROOVE_FX_MIXER) return fail(ctx, std::string(who) + ": a Mixer is the identity and launches nothing: it reads no wet-dry-mix");
+  return 0;
+}
+int groove_ctl_wet_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
+  const char* who = "groove_ctl_wet_link_create";
+  if (ctl_link_check(ctx, who, src, n_src, target, out) || wet_link_check_target(ctx, who, target) || ctl_link_check_sources(ctx, who, src, n_src)) return 1;
+  if (ctl_link_make(ctx, who, src, n_src, target, GROOVE_CTL_FX_WET, false, out)) return 1;
+  ++target->wet_links;
+  return 0;
+}
+int groove_ctl_wet_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src, groove_fx* target,
+                               groove_ctl_link** out) {
+  const char* who = "groove_ctl_wet_trip_create";
+  if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
+  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, std::string(who) + ": the target is not a live effect of this context");
+  if (n_src != 1 && n_src != target->n) return fail(ctx, std::string(who) + ": n_src must be the target's lane count, or 1 (broadcast)");
+  if (wet_link_check_target(ctx, who, target) || ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src)) return 1;
+  GHIP(ctx, hipSetDevice(ctx->device));
+  groove_ctl_link* l = nullptr;
+  if (ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, GROOVE_CTL_FX_WET, &l)) return 1;
+  l->target = target;
+  ++target->wet_links;
+  ctx->links.push_back(l);
+  *out = l;
+  return 0;
+}
 int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t frames) {
   if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
   groove_ctx* ctx = l->ctx;
@@ -2836,6 +2912,8 @@ int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t fram
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+// The float words a plain effect link writes: the wet-dry mix for a wet link, parameter A otherwise.
+static float* ctl_float_words(const groove_ctl_link* l, groove_fx* fx) { return l->control_index == GROOVE_CTL_FX_WET ? fx->d_wet : fx->d_fa; }
 int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   if (!l) return fail(nullptr, "groove_ctl_link_apply: link is NULL");
   groove_ctx* ctx = l->ctx;
@@ -2856,7 +2934,7 @@ int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
   }
   const bool as_uint = ctl_target_is_uint(l->control_index);
   hipLaunchKernelGGL(ctl_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
-                     as_uint ? nullptr : fx->d_fa, as_uint ? fx->d_ua : nullptr, fx->n);
+                     as_uint ? nullptr : ctl_float_words(l, fx), as_uint ? fx->d_ua : nullptr, fx->n);
   GHIP(ctx, hipGetLastError());
   return 0;
 }
@@ -2968,7 +3046,7 @@ int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
                        (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n);
   } else {
     const bool as_uint = ctl_target_is_uint(l->control_index);
-    hipLaunchKernelGGL(ctl_trip_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, as_uint ? nullptr : fx->d_fa,
+    hipLaunchKernelGGL(ctl_trip_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, as_uint ? nullptr : ctl_float_words(l, fx),
                        as_uint ? fx->d_ua : nullptr, fx->n);
   }
   GHIP(ctx, hipGetLastError());
@@ -3079,6 +3157,11 @@ int groove_ctl_link_destroy(groove_ctl_link* l) {
   if (l->bank && l->control_index == GROOVE_CTL_WELSH_CUTOFF && std::find(ctx->banks.begin(), ctx->banks.end(), l->bank) != ctx->banks.end() &&
       l->bank->cutoff_links && --l->bank->cutoff_links == 0 && ctx->f32_filter)
     (void)bank_replan(l->bank);
+  // the last wet link off a live effect: a reverb is all wet again when the host's copy says so (fx_needs_dry); an effect that died
+  // first cleared l->target (groove_fx_destroy)
+  if (!l->on_bank && l->target && l->control_index == GROOVE_CTL_FX_WET && std::find(ctx->fxs.begin(), ctx->fxs.end(), l->target) != ctx->fxs.end() &&
+      l->target->wet_links)
+    --l->target->wet_links;
   (void)hipStreamSynchronize(ctx->stream); // the link's kernels run there
   auto it = std::find(ctx->links.begin(), ctx->links.end(), l);
   if (it != ctx->links.end()) ctx->links.erase(it);

@@ -1465,6 +1465,15 @@ __global__ __launch_bounds__(kThreads) void fx_reverb_kernel(
 // block is read and written once instead of once per stage.  A thread owns V adjacent lane-channels of one frame
 // (V = 4 when the lane count allows 16-byte accesses).  A reverb ends its run: its comb sum goes to `dst` (the
 // reverb's staging block when the direct all-pass kernel follows, the block itself otherwise).
+// DRY (groove_set_fx_wet_reverb_run: a reverb with a lane below wet 1, or with a live wet link, in the run): the reverb stage also
+// stores its input to `dry`, and the kernel that writes the reverb's final output for a frame applies fx_reverb_kernel's own wet-dry
+// expression to it (fx_wet_mix: the same operations in the same order, the same bits).  Where `dry` lives, and why nothing else
+// touches it in between: the direct forms keep it in the block itself — the run thread stores to the element of `src` it has just
+// read (no other thread of the launch reads or writes that element: every thread loads only its own), and the direct all-pass
+// kernel, which reads OTHER frames only from the staging block, loads its own (frame, lane) element of `dst` before it stores there;
+// the chunked and sequential forms have the comb sum in the block, so `dry` is the reverb's staging block, which those all-pass
+// kernels only read.  DRY = false is the body without any of this: an all-wet reverb executes what it always has.
+__device__ __forceinline__ float fx_wet_mix(float out, float wm, float dry) { return wm < 1.0f ? fmaf(out, wm, dry * (1.0f - wm)) : out; }
 template <int V> struct VecF { float v[V]; };
 template <int V> __device__ __forceinline__ VecF<V> vload(const float* p) {
   VecF<V> r;
@@ -1518,6 +1527,8 @@ struct FxRunArgs {
   const float* src;
   float* dst;
   size_t src_chs, dst_chs;
+  float* dry;           // DRY launches: where the reverb stage leaves its input
+  size_t dry_chs;
   uint32_t n_stages, n;
   float* rows;          // not null: the launch also leaves the block's lane sums, rows[wg_per_ch][2][frames] (fx_row_sum)
   uint32_t frames, wg_per_ch;
@@ -1536,7 +1547,7 @@ __device__ __forceinline__ void fx_row_sum(float mine, float* __restrict__ rows,
   __syncthreads();
   if (threadIdx.x == 0) rows[((size_t)group * 2 + ch) * frames + f] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-template <int V>
+template <int V, bool DRY>
 __device__ __forceinline__ float fx_run_element(const FxRunArgs& a, uint32_t ch, uint32_t lane, uint32_t f) {
   const uint32_t t = ch * a.n + lane;
   const size_t ln = 2 * (size_t)a.n;
@@ -1546,7 +1557,8 @@ __device__ __forceinline__ float fx_run_element(const FxRunArgs& a, uint32_t ch,
     if ((uint32_t)s >= a.n_stages) break;
     const FxRunStage& st = a.st[s];
     VecF<V> y;
-    if (st.kind == GROOVE_FX_REVERB) { // the four combs; only taken when every lane is fully wet
+    if (st.kind == GROOVE_FX_REVERB) { // the four combs; without DRY only taken when every lane is fully wet
+      if constexpr (DRY) vstore<V>(a.dry + ch * a.dry_chs + (size_t)f * a.n + lane, x);
       const VecF<V> att = vload<V>(st.fa + lane);
       VecF<V> in;
 #pragma unroll
@@ -1605,26 +1617,32 @@ __device__ __forceinline__ float fx_run_element(const FxRunArgs& a, uint32_t ch,
   for (int j = 0; j < V; ++j) mine += x.v[j];
   return mine;
 }
-template <int V>
+template <int V, bool DRY>
 __global__ __launch_bounds__(kThreads) void fx_run_kernel(FxRunArgs a) {
   const uint32_t ch = blockIdx.x / a.wg_per_ch, group = blockIdx.x % a.wg_per_ch;
   const uint32_t lane = (group * kThreads + threadIdx.x) * V, f = blockIdx.y;
   tp_reduce_prev(a.prev, threadIdx.x, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
   // (every thread of the workgroup reaches the ONE fx_row_sum call below: it holds a barrier)
-  const float mine = lane < a.n ? fx_run_element<V>(a, ch, lane, f) : 0.0f;
+  const float mine = lane < a.n ? fx_run_element<V, DRY>(a, ch, lane, f) : 0.0f;
   if (a.rows) fx_row_sum(mine, a.rows, a.frames, group, ch, f);
 }
 // Reverb, stage 2: the two short Schroeder all-passes (5 ms, 1.7 ms: shorter than a block, so
 // sequential per lane), chunked like the other delay-line kernels.
-template <int C>
+// DRY: the second all-pass writes the frame's final value, so the wet-dry mix is applied there (`dry`: the reverb's staging block,
+// which this kernel only reads; `data` and the rings are the only things it writes).
+template <int C, bool DRY>
 __global__ __launch_bounds__(kThreads) void fx_reverb_allpass_kernel(
-    float* __restrict__ data, uint32_t n, uint32_t frames, size_t ch_stride, float* __restrict__ ring, ReverbGeom geo) {
+    float* __restrict__ data, uint32_t n, uint32_t frames, size_t ch_stride, float* __restrict__ ring, ReverbGeom geo,
+    const float* __restrict__ dry, size_t dry_chs, const float* __restrict__ wet) {
   const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
   if (t >= 2 * n) return;
   const uint32_t ch = t / n, lane = t % n;
   const size_t ln = 2 * (size_t)n;
   float* __restrict__ ptr = data + ch * ch_stride + lane;
   float* __restrict__ rg = ring + t;
+  [[maybe_unused]] const float* __restrict__ dptr = nullptr;
+  [[maybe_unused]] float wm = 1.0f;
+  if constexpr (DRY) { dptr = dry + ch * dry_chs + lane; wm = wet[lane]; }
   uint32_t pos[2] = {geo.w[4], geo.w[5]};
   for (uint32_t f0 = 0; f0 < frames; f0 += C) {
     const uint32_t c_n = min((uint32_t)C, frames - f0);
@@ -1649,6 +1667,7 @@ __global__ __launch_bounds__(kThreads) void fx_reverb_allpass_kernel(
           rg[(geo.base[4 + i] + p) * ln] = v;
           sum = fmaf(-geo.g[4 + i], v, d[i][j]);
         }
+        if constexpr (DRY) sum = fx_wet_mix(sum, wm, dptr[(size_t)(f0 + j) * n]);
         ptr[(size_t)(f0 + j) * n] = sum;
       }
     }
@@ -1666,9 +1685,13 @@ __global__ __launch_bounds__(kThreads) void fx_reverb_allpass_kernel(
 // chunks of stage 1 and then of stage 2 with a barrier between chunks; the arithmetic per frame is
 // the sequential kernel's, so are the bits.  (All waves of a workgroup share one L1, so the barrier
 // makes the ring and block writes of a chunk visible to the next.)
+// DRY: stage 2 writes the frame's final value, so the wet-dry mix is applied there; its loads join the pass's other loads.  `dry` is
+// the reverb's staging block, which this kernel only reads.
 constexpr uint32_t kAllpassThreads = 1024, kAllpassUnroll = 4;
+template <bool DRY>
 __global__ __launch_bounds__(kAllpassThreads) void fx_reverb_allpass_chunked_kernel(
-    float* __restrict__ data, uint32_t n, uint32_t frames, size_t ch_stride, float* __restrict__ ring, ReverbGeom geo, uint32_t T) {
+    float* __restrict__ data, uint32_t n, uint32_t frames, size_t ch_stride, float* __restrict__ ring, ReverbGeom geo, uint32_t T,
+    const float* __restrict__ dry, size_t dry_chs, const float* __restrict__ wet) {
   const uint32_t ln = 2 * n;
   const uint32_t t0 = blockIdx.x * T;
 #pragma unroll
@@ -1682,6 +1705,7 @@ __global__ __launch_bounds__(kAllpassThreads) void fx_reverb_allpass_chunked_ker
         float* px[kAllpassUnroll];
         float* pr[kAllpassUnroll];
         float x[kAllpassUnroll], d[kAllpassUnroll];
+        [[maybe_unused]] float dv[kAllpassUnroll], wm[kAllpassUnroll];
         bool live[kAllpassUnroll];
 #pragma unroll
         for (uint32_t u = 0; u < kAllpassUnroll; ++u) { // all the loads of this pass first: one round trip
@@ -1693,13 +1717,21 @@ __global__ __launch_bounds__(kAllpassThreads) void fx_reverb_allpass_chunked_ker
           pr[u] = rg + (size_t)((w + f) % N) * ln + tt;
           x[u] = live[u] ? *px[u] : 0.0f;
           d[u] = live[u] ? *pr[u] : 0.0f;
+          if constexpr (DRY) {
+            if (i == 1) {
+              dv[u] = live[u] ? dry[ch * dry_chs + (size_t)f * n + lane] : 0.0f;
+              wm[u] = live[u] ? wet[lane] : 1.0f;
+            }
+          }
         }
 #pragma unroll
         for (uint32_t u = 0; u < kAllpassUnroll; ++u) {
           if (live[u]) {
             const float v = fmaf(g, d[u], x[u]);
             *pr[u] = v;
-            *px[u] = fmaf(-g, v, d[u]);
+            float o = fmaf(-g, v, d[u]);
+            if constexpr (DRY) { if (i == 1) o = fx_wet_mix(o, wm[u], dv[u]); }
+            *px[u] = o;
           }
         }
       }
@@ -1731,9 +1763,10 @@ struct AllpassDirectArgs {
   uint32_t n, frames;
   float* rows;          // not null: the block's lane sums, rows[wg_per_ch][2][frames] (fx_row_sum)
   uint32_t wg_per_ch;
+  const float* wet;     // DRY launches: the reverb's per-lane wet-dry mix (the dry value is the thread's own element of `dst`: fx_run_kernel)
   TpPrev prev;          // the all-pass stream (groove_set_fx_allpass_stream): the previous block's lane sums, put on their bus by this launch
 };
-template <int V>
+template <int V, bool DRY>
 __device__ __forceinline__ float allpass_direct_element(const AllpassDirectArgs& a, uint32_t ch, uint32_t lane, uint32_t f) {
   const uint32_t t = ch * a.n + lane;
   const size_t ln = 2 * (size_t)a.n;
@@ -1766,7 +1799,13 @@ __device__ __forceinline__ float allpass_direct_element(const AllpassDirectArgs&
   VecF<V> out;
 #pragma unroll
   for (int k = 0; k < V; ++k) out.v[k] = fmaf(-a.g[1], u.v[k], d.v[k]);
-  vstore<V>(a.dst + ch * a.dst_chs + (size_t)f * a.n + lane, out);
+  float* po = a.dst + ch * a.dst_chs + (size_t)f * a.n + lane;
+  if constexpr (DRY) { // the run left the reverb's input in this very element; nobody else reads or writes it (fx_wet_mix's note)
+    const VecF<V> dry = vload<V>(po), wm = vload<V>(a.wet + lane);
+#pragma unroll
+    for (int k = 0; k < V; ++k) out.v[k] = fx_wet_mix(out.v[k], wm.v[k], dry.v[k]);
+  }
+  vstore<V>(po, out);
   if (f + a.N[0] >= a.frames) vstore<V>(a.ring + (a.new_base[0] + (a.w[0] + f) % a.N[0]) * ln + t, v0);
   if (f + a.N[1] >= a.frames) vstore<V>(a.ring + (a.new_base[1] + slot1) * ln + t, u);
   float mine = 0.0f;
@@ -1774,12 +1813,12 @@ __device__ __forceinline__ float allpass_direct_element(const AllpassDirectArgs&
   for (int k = 0; k < V; ++k) mine += out.v[k];
   return mine;
 }
-template <int V>
+template <int V, bool DRY>
 __global__ __launch_bounds__(kThreads) void fx_reverb_allpass_direct_kernel(AllpassDirectArgs a) {
   tp_reduce_prev(a.prev, threadIdx.x, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
   const uint32_t ch = blockIdx.x / a.wg_per_ch, group = blockIdx.x % a.wg_per_ch;
   const uint32_t lane = (group * kThreads + threadIdx.x) * V, f = blockIdx.y;
-  const float mine = lane < a.n ? allpass_direct_element<V>(a, ch, lane, f) : 0.0f;
+  const float mine = lane < a.n ? allpass_direct_element<V, DRY>(a, ch, lane, f) : 0.0f;
   if (a.rows && f < a.frames) fx_row_sum(mine, a.rows, a.frames, group, ch, f); // (uniform in the workgroup: it holds a barrier)
 }
 

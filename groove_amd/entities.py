@@ -108,6 +108,15 @@ class Context:
         _lib.check(self.L.groove_set_fx_allpass_stream(self.h, 1 if on else 0), self.h)
 
     @property
+    def fx_wet_reverb_run(self):
+        """A partly wet reverb keeps the fused run's forms (include/groove_hip.h groove_set_fx_wet_reverb_run)."""
+        return bool(self.L.groove_fx_wet_reverb_run(self.h))
+
+    @fx_wet_reverb_run.setter
+    def fx_wet_reverb_run(self, on):
+        _lib.check(self.L.groove_set_fx_wet_reverb_run(self.h, 1 if on else 0), self.h)
+
+    @property
     def split_max_waves(self):
         return self.L.groove_split_max_waves(self.h)
 
@@ -416,6 +425,14 @@ class Effect:
         frames = block.cap if frames is None else frames
         return self.ctx.L.groove_fx_kernel_form(self.h, block.h, frames).decode()
 
+    def link_wet(self, sources):
+        """A ControlLink onto this effect's wet-dry-mix (groove_ctl_wet_link_create)."""
+        return ControlLink(self.ctx, sources, self, T.CTL_FX_WET, wet=True)
+
+    def trip_wet(self, lanes, start_beats):
+        """A ControlTripLink onto this effect's wet-dry-mix (groove_ctl_wet_trip_create)."""
+        return ControlTripLink(self.ctx, lanes, start_beats, self, T.CTL_FX_WET, wet=True)
+
     def reset(self):
         _lib.check(self.ctx.L.groove_fx_reset(self.h), self.ctx.h)
 
@@ -430,11 +447,18 @@ class ControlLink:
     once per block -> Controllable.control_set_param_by_index of the target, without a host wait.  `sources` is a ctypes array
     of abi_types.CtlSource, one per target lane or one for all.  derived=True makes it a FILTER link (groove_ctl_filter_link_create):
     onto a filter's cutoff, q or passband-ripple, whose coefficients the link derives on the device.  A target that is an Instrument
-    makes it a BANK link (groove_ctl_bank_link_create): one source, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff."""
+    makes it a BANK link (groove_ctl_bank_link_create): one source, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff.
+    wet=True makes it a WET link (groove_ctl_wet_link_create) onto the effect's wet-dry-mix, which the other creates refuse."""
 
-    def __init__(self, ctx, sources, target, control_index, derived=False):
+    def __init__(self, ctx, sources, target, control_index, derived=False, wet=False):
         self.ctx, self.target, self.n_src, self.derived = ctx, target, len(sources), derived
         h = C.c_void_p()
+        if wet:
+            if control_index != T.CTL_FX_WET or derived or isinstance(target, Instrument):
+                raise ValueError("a wet link reaches an Effect's wet-dry-mix (CTL_FX_WET)")
+            _lib.check(ctx.L.groove_ctl_wet_link_create(ctx.h, sources, len(sources), target.h, C.byref(h)), ctx.h)
+            self.h = h
+            return
         create = ctx.L.groove_ctl_filter_link_create if derived else ctx.L.groove_ctl_link_create
         if isinstance(target, Instrument):
             create = ctx.L.groove_ctl_bank_link_create
@@ -464,15 +488,22 @@ class ControlTripLink:
     steps (kind, start, end, beats) per source lane — one lane for every target lane, or one for all — and `start_beats` the lanes'
     start beats (a number: the same for all).  work(at_units) is IsController.work for the block that starts at that musical time,
     abi_types.CTL_UNITS_PER_BEAT units per beat.  A target that is an Instrument makes it a BANK trip (groove_ctl_bank_trip_create):
-    one lane, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff."""
+    one lane, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff.  wet=True makes it a WET trip (groove_ctl_wet_trip_create)
+    onto the effect's wet-dry-mix, which the other creates refuse."""
 
-    def __init__(self, ctx, lanes, start_beats, target, control_index):
+    def __init__(self, ctx, lanes, start_beats, target, control_index, wet=False):
         self.ctx, self.target, self.n_src = ctx, target, len(lanes)
         steps, n_steps = T.ctl_steps(lanes)
         if not isinstance(start_beats, (list, tuple)):
             start_beats = [start_beats] * len(lanes)
         starts = (C.c_double * len(lanes))(*start_beats)
         h = C.c_void_p()
+        if wet:
+            if control_index != T.CTL_FX_WET or isinstance(target, Instrument):
+                raise ValueError("a wet trip reaches an Effect's wet-dry-mix (CTL_FX_WET)")
+            _lib.check(ctx.L.groove_ctl_wet_trip_create(ctx.h, steps, n_steps, starts, len(lanes), target.h, C.byref(h)), ctx.h)
+            self.h = h
+            return
         create = ctx.L.groove_ctl_bank_trip_create if isinstance(target, Instrument) else ctx.L.groove_ctl_trip_create
         _lib.check(create(ctx.h, steps, n_steps, starts, len(lanes), target.h, control_index, C.byref(h)), ctx.h)
         self.h = h

@@ -439,7 +439,8 @@ void Orchestrator::place_trips() {
     if (bank_of(t->target())) return instrument_controls_on_device_ && bank_control_device_linkable((int)t->control_index());
     if (!trips_on_device_ || !fx_of(t->target())) return false;
     const uint32_t kind = static_cast<FxEffect*>(get(t->target()))->kind();
-    return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index());
+    return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index()) ||
+           (wet_links_on_device_ && fx_control_device_wet(kind, (int)t->control_index()));
   };
   // the effects and instruments that ANY control reaches through the host: a trip the library cannot take, a `controls` link without a device link
   std::vector<char> host_path(nodes_.size(), 0);
@@ -456,8 +457,10 @@ void Orchestrator::place_trips() {
     const double start = t->start_beat();
     groove_ctl_link* link = nullptr;
     groove_bank* bank = bank_of(t->target());
-    if (bank ? groove_ctl_bank_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, bank, t->control_index(), &link)
-             : groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
+    const bool wet = !bank && t->control_index() == GROOVE_CTL_FX_WET; // (reachable: only with set_wet_links_on_device)
+    if (bank  ? groove_ctl_bank_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, bank, t->control_index(), &link)
+        : wet ? groove_ctl_wet_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), &link)
+              : groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
       // the library has the last word (a step it refuses: zero beats, a Triggered step; a bank that is no Welsh bank): this target's trips all stay on the host
       host_path[t->target()] = 1;
       for (ControlTrip* u : trips)
@@ -489,6 +492,12 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
     src->add_link({link, target, (uint32_t)idx});
     return 0;
   }
+  if (fx && wet_links_on_device_ && fx_control_device_wet(static_cast<FxEffect*>(te)->kind(), idx)) {
+    groove_ctl_link* link = nullptr;
+    if (groove_ctl_wet_link_create(ctx_, &desc, 1, fx, &link)) return fail(groove_last_error(ctx_));
+    src->add_link({link, target, (uint32_t)idx});
+    return 0;
+  }
   groove_bank* bank = te->is_instrument() ? static_cast<Instrument*>(te)->fused_bank() : nullptr;
   if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(idx)) {
     groove_ctl_link* link = nullptr;
@@ -506,6 +515,11 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
   src->add_link({nullptr, target, (uint32_t)idx});
   return 0;
 }
+int Orchestrator::set_wet_reverb_run(bool on) {
+  if (groove_set_fx_wet_reverb_run(ctx_, on ? 1 : 0)) return fail(groove_last_error(ctx_));
+  return 0;
+}
+bool Orchestrator::wet_reverb_run() const { return groove_fx_wet_reverb_run(ctx_) != 0; }
 int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units, bool on_instrument) {
   if (deferring_ && !on_instrument) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
   if (trip_units ? groove_ctl_trip_apply(link, at) : groove_ctl_link_apply(link, at)) return fail(groove_last_error(ctx_));
@@ -808,6 +822,10 @@ void gh_set_render_ahead(void* h, int mode) { ((Orchestrator*)h)->set_render_ahe
 void gh_set_fused_direct(void* h, int on) { ((Orchestrator*)h)->set_fused_direct(on != 0); }
 void gh_set_filter_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_filter_links_on_device(on != 0); }
 void gh_set_trips_on_device(void* h, int on) { ((Orchestrator*)h)->set_trips_on_device(on != 0); }
+void gh_set_wet_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_wet_links_on_device(on != 0); }
+int gh_wet_links_on_device(void* h) { return ((Orchestrator*)h)->wet_links_on_device() ? 1 : 0; }
+int gh_set_wet_reverb_run(void* h, int on) { return ((Orchestrator*)h)->set_wet_reverb_run(on != 0); }
+int gh_wet_reverb_run(void* h) { return ((Orchestrator*)h)->wet_reverb_run() ? 1 : 0; }
 void gh_set_instrument_controls_on_device(void* h, int on) { ((Orchestrator*)h)->set_instrument_controls_on_device(on != 0); }
 // 1: the trip has been device-resident since the last skip_to_start (a run's start); 0: it goes through the host (or is no trip)
 int gh_control_trip_on_device(void* h, int uid) {

@@ -105,6 +105,9 @@ inline bool fx_control_device_linkable(uint32_t fx_kind, int index) {
 
 // The parameters a FILTER link reaches (groove_ctl_filter_link_create, which has the last word): cutoff onto the nine filter kinds, q onto the
 // kinds whose formula reads it, passband-ripple onto the 24 dB low-pass.
+// wet-dry-mix onto every kind whose kernels read it (groove_ctl_wet_link_create / groove_ctl_wet_trip_create, which have the last word): all
+// but the Mixer, which launches nothing.  Only where the orchestrator has been asked to: Orchestrator::set_wet_links_on_device.
+inline bool fx_control_device_wet(uint32_t fx_kind, int index) { return index == GROOVE_CTL_FX_WET && fx_kind != GROOVE_FX_MIXER; }
 inline bool fx_control_device_derived(uint32_t fx_kind, int index) {
   const bool lp24 = fx_kind == GROOVE_FX_BIQUAD_LP24;
   const bool bq12 = fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || (fx_kind >= GROOVE_FX_BIQUAD_BP12 && fx_kind <= GROOVE_FX_BIQUAD_HSHELF12);
@@ -426,6 +429,15 @@ class Orchestrator {
   // effect (trips and `controls` links) is device-resident too — one host-path groove_fx_set_param re-uploads the host's stale copy of the
   // parameter the device trip owns.  Everything else (instruments, wet-dry-mix) takes the host path unchanged.  Off by default.
   void set_trips_on_device(bool on) { trips_on_device_ = on; }
+  // Controls onto an effect's wet-dry-mix stay on the device (groove_ctl_wet_link_create, groove_ctl_wet_trip_create).  link_control then
+  // links an LFO or a signal-passthrough source onto it there — a sidechain onto the mix is linked (0) where it is dropped (2) with the
+  // switch off — and place_trips counts a trip onto it as reachable when set_trips_on_device is on as well, so that it no longer forces
+  // the effect's other trips onto the host.  Alone it moves no trip.  Off by default; it affects the links made after it is set.
+  void set_wet_links_on_device(bool on) { wet_links_on_device_ = on; }
+  bool wet_links_on_device() const { return wet_links_on_device_; }
+  // The library's groove_set_fx_wet_reverb_run: a partly wet reverb (and one with a live wet link) keeps the fused run's forms.  Off by default.
+  int set_wet_reverb_run(bool on);
+  bool wet_reverb_run() const;
   bool trips_on_device() const { return trips_on_device_; }
   // Controls onto a Welsh synth's dca-gain / gain, dca-pan / pan or filter-cutoff / cutoff stay on the device (groove_ctl_bank_trip_create,
   // groove_ctl_bank_link_create): no groove_bank_set_param — a re-derivation, a re-plan and a re-upload of the bank, with their host waits —
@@ -482,6 +494,7 @@ class Orchestrator {
   bool fused_direct_ = true;
   bool filter_links_on_device_ = false;
   bool trips_on_device_ = false;
+  bool wet_links_on_device_ = false;
   bool instrument_controls_on_device_ = false;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead

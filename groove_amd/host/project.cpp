@@ -436,7 +436,7 @@ ProjectDesc parse_project(const std::string& text, const std::string& assets_roo
       else if (src->kind == "lfo") c.route = ProjectDesc::CONTROL_PER_BLOCK;
       else { // the host derives that parameter's device form: a sample of a device block would have to come back to it in every block
         p.warnings.push_back("control " + c.id + " dropped: a signal source onto '" + c.param + "' would need a download per block");
-        if (dst->is_effect && fx_control_device_derived(dst->fx_kind, idx)) p.held_controls.push_back({c, p.warnings.size() - 1});
+        if (dst->is_effect && (fx_control_device_derived(dst->fx_kind, idx) || fx_control_device_wet(dst->fx_kind, idx))) p.held_controls.push_back({c, p.warnings.size() - 1});
         continue;
       }
       p.controls.push_back(c);
@@ -673,12 +673,12 @@ int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets
     if (src == uid_of.end() || dst == uid_of.end()) continue; // (parse_project has warned)
     if (o.link_control(src->second, dst->second, c.param) == 1) return 1;
   }
-  if (o.filter_links_on_device())
-    for (const auto& h : p.held_controls) {
-      auto src = uid_of.find(h.control.source), dst = uid_of.find(h.control.target);
-      if (src == uid_of.end() || dst == uid_of.end()) continue;
-      if (o.link_control(src->second, dst->second, h.control.param) == 1) return 1;
-    }
+  for (const auto& h : p.held_controls) { // a filter parameter with set_filter_links_on_device, wet-dry-mix with set_wet_links_on_device
+    if (!(held_control_is_wet(h.control) ? o.wet_links_on_device() : o.filter_links_on_device())) continue;
+    auto src = uid_of.find(h.control.source), dst = uid_of.find(h.control.target);
+    if (src == uid_of.end() || dst == uid_of.end()) continue;
+    if (o.link_control(src->second, dst->second, h.control.param) == 1) return 1;
+  }
   for (const auto& cable : p.patch_cables)
     for (size_t i = 0; i + 1 < cable.size(); ++i) {
       auto a = uid_of.find(cable[i]), b = uid_of.find(cable[i + 1]);

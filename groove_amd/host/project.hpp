@@ -55,13 +55,16 @@ struct ProjectDesc {
   std::vector<Trip> trips;
   std::vector<ControllerDev> controllers;
   std::vector<Control> controls; // the links that resolve (the others are warnings)
-  // signal source -> a filter's cutoff / q / passband-ripple: dropped with a warning (`warning` is its index in `warnings`), and kept here
-  // for an orchestrator that derives filter links on the device (Orchestrator::set_filter_links_on_device): instantiate() links them there
+  // signal source -> a filter's cutoff / q / passband-ripple, or an effect's wet-dry-mix: dropped with a warning (`warning` is its index in
+  // `warnings`), and kept here for an orchestrator that keeps such links on the device (Orchestrator::set_filter_links_on_device for the
+  // filter parameters, set_wet_links_on_device for wet-dry-mix: held_control_is_wet): instantiate() links them there
   struct HeldControl { Control control; size_t warning; };
   std::vector<HeldControl> held_controls;
   std::vector<std::string> warnings; // the reference eprintln!s and continues (songs.rs:137, 152-156)
 };
 
+// Which switch a held control waits for: wet-dry-mix -> set_wet_links_on_device, the filter parameters -> set_filter_links_on_device.
+inline bool held_control_is_wet(const ProjectDesc::Control& c) { return fx_control_index_for_name(c.param) == GROOVE_CTL_FX_WET; }
 // WelshPatchSettings::derive_welsh_synth_params (settings/src/patches.rs:87-170).
 groove_welsh_params welsh_params_from_patch_json(const json5::Value& patch, std::vector<std::string>* warnings);
 // WelshPatchSettings::patch_name_to_settings_name (patches.rs:51-55): "ElectricPiano" → "electric-piano".
@@ -88,7 +91,8 @@ bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* s
 // The instantiate() half: devices → entities, patch cables, MIDI routing, tracks → Sequencer,
 // trips → ControlTrip.  With `synthetic_kit` the drumkit uses a generated sample bank instead of
 // <assets>/samples/elphnt.io/707 (the GPU box has no reference assets).
-// With Orchestrator::set_filter_links_on_device(true) set beforehand, the project's held_controls are linked too.
+// With Orchestrator::set_filter_links_on_device(true) / set_wet_links_on_device(true) set beforehand, the project's held_controls onto
+// filter parameters / wet-dry-mix are linked too.
 int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets_root, bool synthetic_kit);
 
 } // namespace groove_host

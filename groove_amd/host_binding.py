@@ -29,6 +29,8 @@ def load():
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
         "gh_set_trips_on_device": (None, [vp, i]), "gh_control_trip_on_device": (i, [vp, i]),
         "gh_set_instrument_controls_on_device": (None, [vp, i]),
+        "gh_set_wet_links_on_device": (None, [vp, i]), "gh_wet_links_on_device": (i, [vp]),
+        "gh_set_wet_reverb_run": (i, [vp, i]), "gh_wet_reverb_run": (i, [vp]),
         "gh_debug_info": (i, [vp, C.c_char_p, C.c_size_t]), "gh_connect_midi_downstream": (i, [vp, i, i]),
         "gh_add_timer": (i, [vp, d]), "gh_add_sequencer": (i, [vp]),
         "gh_sequencer_insert": (i, [vp, i, i, i, d, d]), "gh_sequencer_set_end": (i, [vp, i, d]),
@@ -107,6 +109,20 @@ class Orchestrator:
         says how it went — LFO links when they are made, so set it before link_control.  Off by default; independent of
         set_trips_on_device."""
         self.L.gh_set_instrument_controls_on_device(self.h, 1 if on else 0)
+
+    def set_wet_links_on_device(self, on):
+        """Controls onto an effect's wet-dry-mix stay on the device: link_control links an LFO or a signal source onto it there (a signal
+        source is dropped without), and — with set_trips_on_device — a trip onto it is device-resident and no longer keeps the effect's
+        other trips on the host.  Off by default; set it before link_control."""
+        self.L.gh_set_wet_links_on_device(self.h, 1 if on else 0)
+
+    def wet_links_on_device(self): return bool(self.L.gh_wet_links_on_device(self.h))
+
+    def set_wet_reverb_run(self, on):
+        """The library's groove_set_fx_wet_reverb_run: a partly wet reverb keeps the fused run's kernel forms (same bits).  Off by default."""
+        self._chk(self.L.gh_set_wet_reverb_run(self.h, 1 if on else 0))
+
+    def wet_reverb_run(self): return bool(self.L.gh_wet_reverb_run(self.h))
 
     def control_trip_on_device(self, uid):
         """1: the trip has been device-resident since the last run started; 0: it goes through the host."""

@@ -42,6 +42,8 @@ SYMBOLS = {
     "groove_look_ahead": (_u32, [_vp]),
     "groove_set_fx_allpass_stream": (_i, [_vp, _i]),
     "groove_fx_allpass_stream": (_i, [_vp]),
+    "groove_set_fx_wet_reverb_run": (_i, [_vp, _i]),
+    "groove_fx_wet_reverb_run": (_i, [_vp]),
     "groove_set_split_max_waves": (_i, [_vp, _u32]),
     "groove_split_max_waves": (_u32, [_vp]),
     "groove_bank_kernel_form": (C.c_char_p, [_vp, _u32, _i]),
@@ -99,6 +101,8 @@ SYMBOLS = {
     "groove_ctl_trip_apply": (_i, [_vp, C.c_uint64]),
     "groove_ctl_bank_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _u32, _vpp]),
     "groove_ctl_bank_trip_create": (_i, [_vp, C.POINTER(T.CtlStep), _u32, C.POINTER(C.c_double), _u32, _vp, _u32, _vpp]),
+    "groove_ctl_wet_link_create": (_i, [_vp, C.POINTER(T.CtlSource), _u32, _vp, _vpp]),
+    "groove_ctl_wet_trip_create": (_i, [_vp, C.POINTER(T.CtlStep), _u32, C.POINTER(C.c_double), _u32, _vp, _vpp]),
     "groove_ctl_link_reset": (_i, [_vp]),
     "groove_ctl_link_destroy": (_i, [_vp]),
     "groove_mix": (_i, [_vp, _vpp, _u32, _u32, _vp, _i]),

@@ -118,6 +118,16 @@ uint32_t groove_look_ahead(groove_ctx* ctx);
  * Default off.  No reference counterpart (the reference transforms one sample at a time, orchestrator.rs:446-454). */
 int groove_set_fx_allpass_stream(groove_ctx* ctx, int on);
 int groove_fx_allpass_stream(groove_ctx* ctx);
+/* Tuning: on = a reverb that is only PARTLY wet (a lane's wet-dry-mix below 1, or a live wet link onto it: groove_ctl_wet_link_create)
+ * keeps the forms of an all-wet one — its combs a stage of the fused run, the all-pass kernels behind it, the all-pass stream, the
+ * block's lane sums left for groove_mix — where, off, it walks the block's frames serially (fx_reverb_kernel) and cuts the chain's
+ * fused run in front of it.  The run's reverb stage then also keeps its input, and the kernel that writes the reverb's final value
+ * applies the serial kernel's own `wet < 1 ? fma(out, wet, dry * (1 - wet)) : out` per lane: results are bit-identical either way.
+ * groove_fx_kernel_form reports the all-wet reverb's form strings for it.  An all-wet reverb launches exactly what it launches with
+ * the knob off.  Default off; GROOVE_FX_WET_REVERB_RUN=1 in the environment sets it at groove_init.  May be changed between any two
+ * blocks.  No reference counterpart (the reference transforms one sample at a time, orchestrator.rs:446-454). */
+int groove_set_fx_wet_reverb_run(groove_ctx* ctx, int on);
+int groove_fx_wet_reverb_run(groove_ctx* ctx);
 /* Tuning: Welsh banks of up to this many (virtual) wavefronts that are too big for the time-parallel form render ROLE-SPLIT:
  * four wavefronts per 64 voices — envelopes + LFO, oscillators, cutoff tangent + coefficient quotients, filter + gains — pipelined
  * over the block's frames through LDS, so that a bank which cannot fill the chip with voices fills it with the parts of a voice's
@@ -316,7 +326,8 @@ int groove_fx_set_params(groove_fx* fx, const groove_fx_params* p, uint32_t n);
  *   src[n_src]: n_src equals the target's lane count, or is 1 and is broadcast to every lane; all of one `source` kind.
  *   control_index: GROOVE_CTL_FX_CEILING (Gain), _BITS (Bitcrusher), _ATTENUATION (Reverb), _THRESHOLD (Compressor / Limiter)
  *   — the parameters whose device form IS the value.  _CUTOFF, _Q, _PASSBAND_RIPPLE (coefficients derived on the host in f64)
- *   and _WET (it chooses a kernel path on the host) are refused, as are noise / none waveforms (no closed form for the state
+ *   and _WET (it chooses a reverb's kernel path on the host) are refused here — the first three have groove_ctl_filter_link_create,
+ *   _WET has groove_ctl_wet_link_create, both below — as are noise / none waveforms (no closed form for the state
  *   of a noise generator after n ticks).
  * A link does not update the host's copy of the target's parameters: a later groove_fx_set_param / groove_fx_set_params on the
  * target re-uploads that copy and so overwrites the linked parameter until the link's next apply. */
@@ -330,7 +341,7 @@ int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32
  * groove_fx_set_param(s) refresh it with the coefficients, so the staleness rule above holds unchanged, and two links onto one
  * effect (cutoff and q) see each other's last value in the order of their applies.
  *   control_index: GROOVE_CTL_FX_CUTOFF onto any of the nine filter kinds, _Q onto low-pass / high-pass / all-pass 12 dB,
- *   _PASSBAND_RIPPLE onto low-pass 24 dB.  Everything else is refused (_WET included).  The sources are checked as above.
+ *   _PASSBAND_RIPPLE onto low-pass 24 dB.  Everything else is refused (_WET included: groove_ctl_wet_link_create).  The sources are checked as above.
  * The link it returns is an ordinary one: capture, apply, reset and destroy below. */
 int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
                                   groove_ctl_link** out);
@@ -350,7 +361,7 @@ int groove_ctl_link_apply(groove_ctl_link* link, uint64_t at_frame);
  *   uploaded once; they do not depend on the sample rate.
  *   control_index: ONE create for both forms — a parameter whose device form is the value (groove_ctl_link_create's list) makes a
  *   plain link, a filter's cutoff, q or passband-ripple (groove_ctl_filter_link_create's list) a filter link with the parameter shadow.
- * Refused: _WET; a parameter the target's kind does not have; n_steps == 0 or > 65,536; a step with beats <= 0 or a non-finite
+ * Refused: _WET (groove_ctl_wet_trip_create takes it); a parameter the target's kind does not have; n_steps == 0 or > 65,536; a step with beats <= 0 or a non-finite
  * beats, start or end; a non-finite start_beat; an unknown step kind; a target that is not a live effect.
  * The value is clamped to 0..1 and goes through groove_fx_set_param's law in the precision it has there, so the target word is the one
  * that call would give it (flat and slope steps: bit for bit; the two curves read log10 from the device's math library).  The link it
@@ -396,6 +407,19 @@ int groove_ctl_bank_link_create(groove_ctx* ctx, const groove_ctl_source* src, u
                                 groove_ctl_link** out);
 int groove_ctl_bank_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
                                 groove_bank* target, uint32_t control_index, groove_ctl_link** out);
+/* A WET link / WET trip: a controller linked to an effect's wet-dry-mix (GROOVE_CTL_FX_WET), which the three creates above refuse.
+ * Every effect kernel reads the per-lane mix from device memory at launch and selects `wet < 1` per lane, so the link's apply is the
+ * plain link's kernel writing that array: groove_fx_set_param's law, (float)clamp01(v), no host wait, no copy.  The one decision the
+ * HOST takes from the value is a reverb's kernel form, so a reverb counts its live wet links: while it has one it is treated as not
+ * all wet whatever the host's copy says — serial with groove_set_fx_wet_reverb_run off, the fused run's forms with it on — and it is
+ * all wet again once the last link is destroyed and the host's copy says so.
+ *   Targets: every kind but GROOVE_FX_MIXER (the identity launches nothing and reads no mix).  Sources, steps and n_src are checked
+ *   as by groove_ctl_link_create / groove_ctl_trip_create.
+ * The staleness rule holds unchanged: a later groove_fx_set_param(s) re-uploads the host's copy, the link's next apply overwrites it.
+ * The link returned is an ordinary one: capture, apply / trip apply, reset and destroy under their own rules. */
+int groove_ctl_wet_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out);
+int groove_ctl_wet_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                               groove_fx* target, groove_ctl_link** out);
 /* Resets::reset (Orchestrator::skip_to_start, orchestrator.rs:971-983): a signal link forgets what it captured. */
 int groove_ctl_link_reset(groove_ctl_link* link);
 /* Orchestrator::unlink_control (orchestrator.rs:1296-1320).  groove_shutdown frees the links that are still alive. */
