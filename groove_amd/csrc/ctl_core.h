@@ -174,4 +174,59 @@ GROOVE_HD void pan_gains(double gain, double pan, float& gl, float& gr) {
 // The bank's (gain, pan) shadow on the device, [word][lane] in internal lane order (groove_bank: d_dca).
 enum : uint32_t { CTL_DCA_GAIN = 0, CTL_DCA_PAN = 1, CTL_DCA_WORDS = 2 };
 
+// ------------------------------------------------------------------ targets on an FM or a sampler bank
+// The same two creates reach an FM bank's dca-gain, dca-pan, depth and beta and a sampler (or drumkit) bank's gain, by
+// groove_bank_set_param's laws for those kinds: the float groove_fm_params / groove_sampler_params would hold.  gain and pan are the
+// Welsh laws above; depth is a Normal and beta a plain ParameterType set from the ControlValue as it is — (float)clamp01(v) both (spec
+// decisions, docs/DSP_SPEC.md section 13); `ratio` has no law anywhere and no control.
+GROOVE_HD bool ctl_fm_target_ok(uint32_t control_index) { return control_index >= GROOVE_CTL_FM_DCA_GAIN && control_index <= GROOVE_CTL_FM_BETA; }
+GROOVE_HD bool ctl_sampler_target_ok(uint32_t control_index) { return control_index == GROOVE_CTL_SAMPLER_GAIN; }
+GROOVE_HD float ctl_fm_depth_f64(double value) { return (float)clamp01d(value); }
+GROOVE_HD float ctl_fm_beta_f64(double value) { return (float)clamp01d(value); }
+GROOVE_HD float ctl_sampler_gain_f64(double value) { return (float)clamp01d(value); }
+GROOVE_HD float ctl_fm_param_f64(uint32_t control_index, double value) {
+  switch (control_index) {
+    case GROOVE_CTL_FM_DCA_GAIN: return ctl_bank_gain_f64(value);
+    case GROOVE_CTL_FM_DCA_PAN: return ctl_bank_pan_f64(value);
+    case GROOVE_CTL_FM_DEPTH: return ctl_fm_depth_f64(value);
+    default: return ctl_fm_beta_f64(value); // GROOVE_CTL_FM_BETA
+  }
+}
+// An FM bank's per-voice shadow on the device, [word][voice] (groove_bank: d_dca with CTL_FM_WORDS rows): the four public floats the
+// derived words come from.  The shadow word of an FM control index is its distance from the first.
+enum : uint32_t { CTL_FM_GAIN = 0, CTL_FM_PAN = 1, CTL_FM_DEPTH = 2, CTL_FM_BETA = 3, CTL_FM_WORDS = 4 };
+GROOVE_HD uint32_t ctl_fm_shadow_word(uint32_t control_index) { return control_index - GROOVE_CTL_FM_DCA_GAIN; }
+// depth x beta -> the modulation index an FM voice multiplies with (FmParams::depth_beta); derive_fm (derive.h) calls this with the
+// floats of the public params, a bank link's kernel with the floats of the shadow.
+GROOVE_HD double fm_depth_beta(float depth, float beta) {
+  GROOVE_NO_CONTRACT
+  return (double)depth * (double)beta;
+}
+// What an apply onto voice e of an FM bank stores: `mine` into its shadow word, the partner word read (gain with pan, depth with beta),
+// and the derived words into the rows of the word-major parameter SoA params[word * n + voice] that every FM kernel loads its FmParams
+// from.  depth_beta is an f64 over TWO 32-bit rows: the low word to the first, the high word to the second.
+GROOVE_HD void ctl_fm_store(uint32_t* params, float* shadow, uint32_t n_voices, uint32_t e, uint32_t control_index, float mine) {
+  constexpr uint32_t kGl = offsetof(FmParams, gl) / 4, kGr = offsetof(FmParams, gr) / 4, kIdx = offsetof(FmParams, depth_beta) / 4;
+  const size_t n = n_voices;
+  const uint32_t word = ctl_fm_shadow_word(control_index), partner = word ^ 1u;
+  shadow[(size_t)word * n + e] = mine;
+  const float other = shadow[(size_t)partner * n + e];
+  if (word <= CTL_FM_PAN) {
+    const bool is_gain = word == CTL_FM_GAIN;
+    float gl, gr;
+    pan_gains((double)(is_gain ? mine : other), (double)(is_gain ? other : mine), gl, gr);
+    params[kGl * n + e] = __builtin_bit_cast(uint32_t, gl);
+    params[kGr * n + e] = __builtin_bit_cast(uint32_t, gr);
+  } else {
+    const bool is_depth = word == CTL_FM_DEPTH;
+    const uint64_t bits = __builtin_bit_cast(uint64_t, fm_depth_beta(is_depth ? mine : other, is_depth ? other : mine));
+    params[kIdx * n + e] = (uint32_t)bits;
+    params[(kIdx + 1u) * n + e] = (uint32_t)(bits >> 32);
+  }
+}
+// ... and onto voice e of a sampler bank: its gain is one word of the record.
+GROOVE_HD void ctl_sampler_store(uint32_t* params, uint32_t n_voices, uint32_t e, float mine) {
+  params[(size_t)(offsetof(SamplerParams, gain) / 4) * n_voices + e] = __builtin_bit_cast(uint32_t, mine);
+}
+
 } // namespace groove

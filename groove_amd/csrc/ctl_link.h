@@ -206,4 +206,45 @@ __global__ __launch_bounds__(kThreads) void ctl_trip_bank_apply_kernel(CtlTrip t
   ctl_bank_store(bank, ctl_bank_param_f64(bank.control_index, v), e);
 }
 
+// ---- FM and sampler bank targets ----------------------------------------------------------------------------------------------
+// A link onto an FM bank's dca-gain, dca-pan, depth or beta, or onto a sampler (drumkit) bank's gain.  Every FM and sampler kernel — serial,
+// time-parallel at one and at four voices per wavefront, the mixed one-launch form, the note-event kernels — loads its record from ONE
+// place, the per-voice SoA params[word * n + voice]: there are no per-wave copies and no plan, so nothing is wave-uniform and the source
+// may have one lane per voice (n_src == n: one drum, one lane) as well as one for all.  One thread per voice; the store is ctl_core.h's
+// ctl_fm_store / ctl_sampler_store, the text the CPU tier holds against derive_fm.  shadow: the FM bank's [CTL_FM_WORDS][n] (nullptr on a
+// sampler bank, whose gain is one word).  A between-blocks mutation ordered like the Welsh one (bank_link_apply).
+struct CtlVoices {
+  uint32_t* __restrict__ params;
+  float* __restrict__ shadow;
+  uint32_t n, control_index;
+};
+__device__ __forceinline__ void ctl_voices_store(const CtlVoices& b, double value, uint32_t e) {
+  if (b.shadow) ctl_fm_store(b.params, b.shadow, b.n, e, b.control_index, ctl_fm_param_f64(b.control_index, value));
+  else ctl_sampler_store(b.params, b.n, e, ctl_sampler_gain_f64(value));
+}
+// An LFO or signal source: the fp32 value01 widened, through groove_bank_set_param's law.
+__global__ __launch_bounds__(kThreads) void ctl_voices_apply_kernel(uint32_t source, CtlLanes src, uint32_t n_src, uint64_t at_frame,
+                                                                    const float* __restrict__ value, const uint32_t* __restrict__ captured,
+                                                                    CtlVoices bank) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= bank.n) return;
+  const uint32_t s = n_src == 1u ? 0u : e;
+  float v;
+  if (source == GROOVE_CTL_SRC_LFO) {
+    v = ctl_lfo_value01(src.waveform[s], src.delta64[s], src.duty64[s], at_frame);
+  } else {
+    if (*captured == 0u) return;
+    v = ctl_signal_value01(src.law[s], value[s]);
+  }
+  ctl_voices_store(bank, (double)v, e);
+}
+// A trip source: the f64 value.  No step of the voice's lane at at_units: its words stay as they are.
+__global__ __launch_bounds__(kThreads) void ctl_trip_voices_apply_kernel(CtlTrip trip, uint32_t n_src, uint64_t at_units, CtlVoices bank) {
+  const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= bank.n) return;
+  double v;
+  if (!ctl_trip_lane_value(trip, n_src, n_src == 1u ? 0u : e, ctl_trip_now(at_units), v)) return;
+  ctl_voices_store(bank, v, e);
+}
+
 } // namespace groove

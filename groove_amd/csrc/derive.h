@@ -168,7 +168,7 @@ inline WelshState initial_welsh_state() {
 
 inline FmParams derive_fm(const groove_fm_params& p, double sr) {
   FmParams o{};
-  o.depth_beta = (double)p.depth * (double)p.beta;
+  o.depth_beta = fm_depth_beta(p.depth, p.beta); // (ctl_core.h: the text a bank link's kernel runs too)
   o.cenv = derive_env(p.carrier_envelope, sr);
   o.menv = derive_env(p.modulator_envelope, sr);
   pan_gains(p.dca_gain, p.dca_pan, o.gl, o.gr);

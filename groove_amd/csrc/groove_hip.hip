@@ -128,7 +128,8 @@ struct groove_bank {
   float* d_pcm = nullptr;   // sampler bank
   // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
   // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
-  // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one)
+  // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one).  fm: the same owner with CTL_FM_WORDS rows — gain, pan, depth,
+  // beta per voice in the caller's order — refreshed by fm_upload_params; a sampler bank has none (its gain is one word of the record)
   float* d_dca = nullptr;
   uint32_t cutoff_links = 0;
   groove_note_event* d_ev[2] = {nullptr, nullptr};
@@ -585,9 +586,44 @@ int welsh_upload_params(groove_bank* b, bool regroup) {
   return 0;
 }
 
+// FM / sampler: derive + upload the parameter SoA only — the state and d_cold stay where they are (groove_bank_set_param).  An FM bank
+// that has a link keeps its (gain, pan, depth, beta) shadow beside the records, from the same host copy.
+std::vector<FmParams> fm_derive_params(const groove_bank* b) {
+  std::vector<FmParams> P(b->n);
+  for (uint32_t v = 0; v < b->n; ++v) P[v] = derive_fm(b->fm[v], b->ctx->sr);
+  return P;
+}
+std::vector<SamplerParams> sampler_derive_params(const groove_bank* b) {
+  std::vector<SamplerParams> P(b->n);
+  for (uint32_t v = 0; v < b->n; ++v) {
+    const groove_sampler_params& sp = b->sampler[v];
+    const groove_sample_desc& d = b->descs[sp.sample_index < b->descs.size() ? sp.sample_index : 0];
+    P[v] = SamplerParams{(uint32_t)d.offset, d.length, (double)d.root_hz, sp.gain, sp.one_shot};
+  }
+  return P;
+}
+int fm_upload_shadow(groove_bank* b) {
+  groove_ctx* ctx = b->ctx;
+  const uint32_t n = b->n;
+  std::vector<float> w((size_t)CTL_FM_WORDS * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const groove_fm_params& p = b->fm[i];
+    w[(size_t)CTL_FM_GAIN * n + i] = p.dca_gain;
+    w[(size_t)CTL_FM_PAN * n + i] = p.dca_pan;
+    w[(size_t)CTL_FM_DEPTH * n + i] = p.depth;
+    w[(size_t)CTL_FM_BETA * n + i] = p.beta;
+  }
+  GHIP(ctx, ctx_memcpy(ctx, b->d_dca, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+int fm_upload_params(groove_bank* b) {
+  if (upload_soa(b->ctx, b->d_params, fm_derive_params(b))) return 1;
+  return b->d_dca ? fm_upload_shadow(b) : 0;
+}
+int sampler_upload_params(groove_bank* b) { return upload_soa(b->ctx, b->d_params, sampler_derive_params(b)); }
+
 int bank_derive_and_upload(groove_bank* b) {
   groove_ctx* ctx = b->ctx;
-  const double sr = ctx->sr;
   const uint32_t n = b->n;
   GHIP(ctx, hipSetDevice(ctx->device));
   if (b->kind == BANK_WELSH) {
@@ -595,22 +631,15 @@ int bank_derive_and_upload(groove_bank* b) {
     if (welsh_upload_params(b, true)) return 1;
     if (upload_soa(ctx, b->d_state, S)) return 1;
   } else if (b->kind == BANK_FM) {
-    std::vector<FmParams> P(n);
     std::vector<FmState> S(n, initial_fm_state());
     std::vector<double> ratio(n);
-    for (uint32_t v = 0; v < n; ++v) { P[v] = derive_fm(b->fm[v], sr); ratio[v] = b->fm[v].ratio; }
-    if (upload_soa(ctx, b->d_params, P)) return 1;
+    for (uint32_t v = 0; v < n; ++v) ratio[v] = b->fm[v].ratio;
+    if (fm_upload_params(b)) return 1;
     if (upload_soa(ctx, b->d_state, S)) return 1;
     GHIP(ctx, ctx_memcpy(ctx, b->d_cold, ratio.data(), ratio.size() * 8, hipMemcpyHostToDevice));
   } else {
-    std::vector<SamplerParams> P(n);
     std::vector<SamplerState> S(n, SamplerState{0, 0, 0, 0});
-    for (uint32_t v = 0; v < n; ++v) {
-      const groove_sampler_params& sp = b->sampler[v];
-      const groove_sample_desc& d = b->descs[sp.sample_index < b->descs.size() ? sp.sample_index : 0];
-      P[v] = SamplerParams{(uint32_t)d.offset, d.length, (double)d.root_hz, sp.gain, sp.one_shot};
-    }
-    if (upload_soa(ctx, b->d_params, P)) return 1;
+    if (sampler_upload_params(b)) return 1;
     if (upload_soa(ctx, b->d_state, S)) return 1;
   }
   b->pending.clear();
@@ -1554,9 +1583,34 @@ int groove_bank_set_param(groove_bank* b, uint32_t voice, uint32_t control_index
   if (!b) return fail(nullptr, "groove_bank_set_param: bank is NULL");
   groove_ctx* ctx = b->ctx;
   if (voice != GROOVE_ALL_VOICES && voice >= b->n) return fail(ctx, "groove_bank_set_param: voice out of range");
-  if (b->kind != BANK_WELSH) return fail(ctx, "groove_bank_set_param: only Welsh banks expose controls");
-  const double v01 = value01 < 0.0 ? 0.0 : (value01 > 1.0 ? 1.0 : value01);
   const uint32_t lo = voice == GROOVE_ALL_VOICES ? 0 : voice, hi = voice == GROOVE_ALL_VOICES ? b->n : voice + 1;
+  if (b->kind != BANK_WELSH) {
+    // an FM bank's four controls, a sampler (drumkit) bank's gain: the laws of ctl_core.h, the ones a bank link's kernel runs
+    if (ctl_bank_target_ok(control_index)) return fail(ctx, "groove_bank_set_param: only Welsh banks expose controls 32 - 34 (dca-gain, dca-pan, filter-cutoff)");
+    const bool fm = b->kind == BANK_FM;
+    if (fm && !ctl_fm_target_ok(control_index))
+      return fail(ctx, ctl_sampler_target_ok(control_index) ? "groove_bank_set_param: an FM bank's controls are 48 - 51 (dca-gain, dca-pan, depth, beta); 64 is a sampler bank's gain"
+                                                            : "groove_bank_set_param: unknown control index");
+    if (!fm && !ctl_sampler_target_ok(control_index))
+      return fail(ctx, ctl_fm_target_ok(control_index) ? "groove_bank_set_param: a sampler bank's control is 64 (gain); 48 - 51 are an FM bank's"
+                                                       : "groove_bank_set_param: unknown control index");
+    for (uint32_t v = lo; v < hi; ++v) {
+      if (!fm) { b->sampler[v].gain = ctl_sampler_gain_f64(value01); continue; }
+      groove_fm_params& p = b->fm[v];
+      const float x = ctl_fm_param_f64(control_index, value01);
+      switch (control_index) {
+        case GROOVE_CTL_FM_DCA_GAIN: p.dca_gain = x; break;
+        case GROOVE_CTL_FM_DCA_PAN: p.dca_pan = x; break;
+        case GROOVE_CTL_FM_DEPTH: p.depth = x; break;
+        default: p.beta = x; break;
+      }
+    }
+    // control-plane path like the Welsh one below: the parameter SoA only — the voices' state and d_cold stay where they are
+    if (ctx_join(ctx)) return 1;
+    GHIP(ctx, ctx_wait(ctx));
+    return fm ? fm_upload_params(b) : sampler_upload_params(b);
+  }
+  const double v01 = value01 < 0.0 ? 0.0 : (value01 > 1.0 ? 1.0 : value01);
   for (uint32_t v = lo; v < hi; ++v) {
     groove_welsh_params& p = b->welsh[v];
     switch (control_index) {
@@ -2248,6 +2302,9 @@ int groove_bank_reset(groove_bank* b) {
   else { const SamplerState s{0, 0, 0, 0}; std::memcpy(w.w, &s, sizeof(s)); }
   hipLaunchKernelGGL(state_fill_kernel, dim3(blocks_for(b->n)), dim3(kThreads), 0, ctx->stream, b->d_state, b->n, b->sw, w);
   GHIP(ctx, hipGetLastError());
+  // An FM bank with links: its shadow goes back to the host's copy, and the records with it — gl, gr and depth_beta each come from TWO
+  // shadow words, so a shadow refreshed alone would pair the host's gain with a pan that the records no longer hold.
+  if (b->kind == BANK_FM && b->d_dca) return fm_upload_params(b);
   return 0;
 }
 uint32_t groove_bank_state_words(groove_bank* b) { return b ? b->sw : 0; }
@@ -3052,12 +3109,24 @@ int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
   GHIP(ctx, hipGetLastError());
   return 0;
 }
-// ---- links onto a Welsh bank (dca-gain, dca-pan, filter-cutoff)
+// ---- links onto a bank: a Welsh bank's dca-gain, dca-pan, filter-cutoff; an FM bank's dca-gain, dca-pan, depth, beta; a sampler bank's gain
 // What both bank creates ask of their target.
 static int bank_link_check(groove_ctx* ctx, const char* who, groove_bank* b, uint32_t n_src, uint32_t control_index) {
   const std::string w = std::string(who) + ": ";
   if (std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, w + "the target is not a live bank of this context");
-  if (b->kind != BANK_WELSH) return fail(ctx, w + "only Welsh banks expose controls (FM and sampler banks have none)");
+  if (b->kind != BANK_WELSH) { // an FM bank's four controls, a sampler (drumkit) bank's gain; one source lane for all voices or one per voice
+    if (ctl_bank_target_ok(control_index)) return fail(ctx, w + "only Welsh banks expose controls 32 - 34 (dca-gain, dca-pan, filter-cutoff)");
+    const bool fm = b->kind == BANK_FM;
+    if (fm ? !ctl_fm_target_ok(control_index) : !ctl_sampler_target_ok(control_index)) {
+      if (fm ? ctl_sampler_target_ok(control_index) : ctl_fm_target_ok(control_index))
+        return fail(ctx, w + (fm ? "an FM bank's controls are 48 - 51 (dca-gain, dca-pan, depth, beta); 64 is a sampler bank's gain"
+                                 : "a sampler bank's control is 64 (gain); 48 - 51 are an FM bank's"));
+      return fail(ctx, w + (fm ? "unknown control index (a link onto an FM bank reaches dca-gain, dca-pan, depth or beta)"
+                               : "unknown control index (a link onto a sampler bank reaches gain)"));
+    }
+    if (n_src != 1 && n_src != b->n) return fail(ctx, w + "n_src must be the bank's voice count, or 1 (broadcast)");
+    return 0;
+  }
   if (!ctl_bank_target_ok(control_index)) return fail(ctx, w + "unknown control index (a bank link reaches dca-gain, dca-pan or filter-cutoff)");
   if (n_src != 1)
     return fail(ctx, w + "n_src must be 1: the value is broadcast to every voice (a per-voice source would break the wave-uniform parameter records; per-voice changes keep groove_bank_set_param)");
@@ -3067,12 +3136,12 @@ static int bank_link_check(groove_ctx* ctx, const char* who, groove_bank* b, uin
 static int bank_link_prepare(groove_bank* b, const char* who, uint32_t control_index) {
   groove_ctx* ctx = b->ctx;
   GHIP(ctx, hipSetDevice(ctx->device));
-  if (control_index == GROOVE_CTL_WELSH_CUTOFF || b->d_dca) return 0;
-  if (hipMalloc(&b->d_dca, (size_t)CTL_DCA_WORDS * b->n * 4) != hipSuccess) {
+  if (control_index == GROOVE_CTL_WELSH_CUTOFF || b->kind == BANK_SAMPLER || b->d_dca) return 0; // (a sampler's gain is one word: no shadow)
+  if (hipMalloc(&b->d_dca, (size_t)(b->kind == BANK_FM ? CTL_FM_WORDS : CTL_DCA_WORDS) * b->n * 4) != hipSuccess) {
     b->d_dca = nullptr;
     return fail(ctx, std::string(who) + ": hipMalloc failed");
   }
-  return welsh_upload_dca(b); // from here on welsh_upload_params keeps it beside the records
+  return b->kind == BANK_FM ? fm_upload_shadow(b) : welsh_upload_dca(b); // from here on welsh_upload_params / fm_upload_params keeps it beside the records
 }
 // The bank re-planned for its count of cutoff links (welsh_plan.h welsh_flag_filter_f32): a control-plane step like groove_bank_set_param's,
 // which it repeats — the host's copy goes up again, the voices' state stays where it is.
@@ -3127,6 +3196,23 @@ static int bank_link_apply(groove_ctl_link* l, const char* who, uint64_t at) {
   GHIP(ctx, hipSetDevice(ctx->device));
   b->ctx_touched = true;
   if (ctx_join(ctx)) return 1;
+  if (b->kind != BANK_WELSH) { // one thread per voice onto the per-voice SoA, the one place every FM and sampler kernel reads (ctl_link.h)
+    const uint32_t ns = l->n_src;
+    const CtlVoices voices{b->d_params, b->kind == BANK_FM ? b->d_dca : nullptr, b->n, l->control_index};
+    const dim3 vgrid(blocks_for(b->n));
+    if (l->source == GROOVE_CTL_SRC_TRIP) {
+      const size_t rows = (size_t)l->n_steps * ns;
+      const double *begin = l->d_trip, *start = begin + rows + ns, *end = start + rows, *beats = end + rows;
+      const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
+      hipLaunchKernelGGL(ctl_trip_voices_apply_kernel, vgrid, dim3(kThreads), 0, ctx->stream, trip, ns, at, voices);
+    } else {
+      const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + (size_t)2 * ns);
+      const CtlLanes lanes{l->d_lanes, l->d_lanes + ns, u, u + ns};
+      hipLaunchKernelGGL(ctl_voices_apply_kernel, vgrid, dim3(kThreads), 0, ctx->stream, l->source, lanes, ns, at, l->d_value, l->d_captured, voices);
+    }
+    GHIP(ctx, hipGetLastError());
+    return 0;
+  }
   const CtlBank bank{b->d_params, b->plan.n_vwaves ? b->d_waves : nullptr, b->d_dca, b->n, b->plan.n_vwaves, l->control_index};
   const dim3 grid(blocks_for(std::max<size_t>(b->n, b->plan.n_vwaves)));
   if (l->source == GROOVE_CTL_SRC_TRIP) {

@@ -314,7 +314,7 @@ class Instrument:
     def note_off(self, voice, key=0, velocity=0):
         self.handle_midi_events(T.note_events([(voice, key, False)]))
 
-    # Controllable
+    # Controllable: the indices of the bank's own kind (abi_types CTL_WELSH_*, CTL_FM_*, CTL_SAMPLER_GAIN); another kind's are refused
     def control_set_param_by_index(self, index, value01, voice=T.ALL_VOICES):
         _lib.check(self.ctx.L.groove_bank_set_param(self.h, voice, index, value01), self.ctx.h)
 
@@ -384,6 +384,8 @@ class WelshSynth(Instrument):
 
 
 class FmSynth(Instrument):
+    """FmSynth::new_with(&FmSynthParams) for n voices.  Controllable: abi_types.CTL_FM_DCA_GAIN, CTL_FM_DCA_PAN, CTL_FM_DEPTH, CTL_FM_BETA."""
+
     def __init__(self, ctx, params):
         h = C.c_void_p()
         _lib.check(ctx.L.groove_fm_create(ctx.h, params, len(params), C.byref(h)), ctx.h)
@@ -391,7 +393,7 @@ class FmSynth(Instrument):
 
 
 class Sampler(Instrument):
-    """Sampler / Drumkit over a shared mono sample bank."""
+    """Sampler / Drumkit over a shared mono sample bank.  Controllable: abi_types.CTL_SAMPLER_GAIN."""
 
     def __init__(self, ctx, pcm, descs, params):
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
@@ -447,7 +449,8 @@ class ControlLink:
     once per block -> Controllable.control_set_param_by_index of the target, without a host wait.  `sources` is a ctypes array
     of abi_types.CtlSource, one per target lane or one for all.  derived=True makes it a FILTER link (groove_ctl_filter_link_create):
     onto a filter's cutoff, q or passband-ripple, whose coefficients the link derives on the device.  A target that is an Instrument
-    makes it a BANK link (groove_ctl_bank_link_create): one source, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff.
+    makes it a BANK link (groove_ctl_bank_link_create): one source, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff; onto
+    an FmSynth's dca-gain, dca-pan, depth or beta or a Sampler's gain, one source for all voices or one per voice.
     wet=True makes it a WET link (groove_ctl_wet_link_create) onto the effect's wet-dry-mix, which the other creates refuse."""
 
     def __init__(self, ctx, sources, target, control_index, derived=False, wet=False):
@@ -488,7 +491,8 @@ class ControlTripLink:
     steps (kind, start, end, beats) per source lane — one lane for every target lane, or one for all — and `start_beats` the lanes'
     start beats (a number: the same for all).  work(at_units) is IsController.work for the block that starts at that musical time,
     abi_types.CTL_UNITS_PER_BEAT units per beat.  A target that is an Instrument makes it a BANK trip (groove_ctl_bank_trip_create):
-    one lane, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff.  wet=True makes it a WET trip (groove_ctl_wet_trip_create)
+    one lane, broadcast, onto a Welsh synth's dca-gain, dca-pan or filter-cutoff; one lane or one per voice onto an FmSynth's or a
+    Sampler's controls.  wet=True makes it a WET trip (groove_ctl_wet_trip_create)
     onto the effect's wet-dry-mix, which the other creates refuse."""
 
     def __init__(self, ctx, lanes, start_beats, target, control_index, wet=False):

@@ -7,7 +7,7 @@
 // a signal source's among them, which are dropped with a warning otherwise.
 // --device-trips: control trips onto effect parameters the library can reach stay on the device (Orchestrator::set_trips_on_device): no
 // host wait per automated block.
-// --device-instrument-controls: control trips and LFO `controls` onto a Welsh synth's dca-gain, dca-pan or filter-cutoff stay on the device
+// --device-instrument-controls: control trips and LFO `controls` onto a Welsh synth's dca-gain, dca-pan or filter-cutoff, an FM synth's gain, pan, depth or beta, a sampler's or drumkit's gain stay on the device
 // (Orchestrator::set_instrument_controls_on_device): no re-plan and re-upload of the synth's bank per automated block.
 //
 // --device-wet-links: `controls` onto an effect's wet-dry-mix stay on the device (Orchestrator::set_wet_links_on_device), a signal source's

@@ -10,9 +10,9 @@
 namespace groove_host {
 
 // ------------------------------------------------------------------ VoiceBankInstrument
-VoiceBankInstrument::VoiceBankInstrument(groove_ctx* ctx, groove_bank* bank, uint32_t voices, bool sum_voices,
+VoiceBankInstrument::VoiceBankInstrument(groove_ctx* ctx, groove_bank* bank, BankControls controls, uint32_t voices, bool sum_voices,
                                          double release_seconds, bool one_voice_per_key)
-    : ctx_(ctx), bank_(bank), voices_(voices), sum_voices_(sum_voices), release_seconds_(release_seconds),
+    : ctx_(ctx), bank_(bank), controls_(controls), voices_(voices), sum_voices_(sum_voices), release_seconds_(release_seconds),
       per_key_(one_voice_per_key), key_of_voice_(voices, -1), busy_until_(voices, 0), started_(voices, 0) {
   groove_block_create(ctx_, voices_, GROOVE_BLOCK_FRAMES, &block_);
   if (sum_voices_) groove_block_create(ctx_, 1, GROOVE_BLOCK_FRAMES, &summed_);
@@ -74,10 +74,10 @@ void VoiceBankInstrument::note_off(uint8_t key, uint8_t velocity, uint64_t now) 
 
 int VoiceBankInstrument::control_index_for_name(const std::string& name) const {
   // #[derive(Control)] kebab-case names, nested fields joined with '-' (proc-macros/src/control.rs:127-131, 165)
-  return bank_control_index_for_name(name);
+  return bank_control_index_for_name(controls_, name);
 }
 int VoiceBankInstrument::control_set_param(uint32_t index, double value01) {
-  return groove_bank_set_param(bank_, GROOVE_ALL_VOICES, index, value01); // (fails, with the library's message, on a bank that has no such control)
+  return groove_bank_set_param(bank_, GROOVE_ALL_VOICES, index, value01); // (fails, with the library's message, on an index of another kind of bank)
 }
 
 // ------------------------------------------------------------------ ToyAudioSource
@@ -436,7 +436,8 @@ void Orchestrator::place_trips() {
   };
   auto reachable = [&](const ControlTrip* t) {
     if (t->steps().empty()) return false;
-    if (bank_of(t->target())) return instrument_controls_on_device_ && bank_control_device_linkable((int)t->control_index());
+    if (bank_of(t->target()))
+      return instrument_controls_on_device_ && bank_control_device_linkable(static_cast<Instrument*>(get(t->target()))->bank_controls(), (int)t->control_index());
     if (!trips_on_device_ || !fx_of(t->target())) return false;
     const uint32_t kind = static_cast<FxEffect*>(get(t->target()))->kind();
     return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index()) ||
@@ -461,7 +462,7 @@ void Orchestrator::place_trips() {
     if (bank  ? groove_ctl_bank_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, bank, t->control_index(), &link)
         : wet ? groove_ctl_wet_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), &link)
               : groove_ctl_trip_create(ctx_, steps.data(), (uint32_t)steps.size(), &start, 1, fx_of(t->target()), t->control_index(), &link)) {
-      // the library has the last word (a step it refuses: zero beats, a Triggered step; a bank that is no Welsh bank): this target's trips all stay on the host
+      // the library has the last word (a step it refuses: zero beats, a Triggered step): this target's trips all stay on the host
       host_path[t->target()] = 1;
       for (ControlTrip* u : trips)
         if (u->target() == t->target()) u->set_device_link(nullptr);
@@ -499,13 +500,13 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
     return 0;
   }
   groove_bank* bank = te->is_instrument() ? static_cast<Instrument*>(te)->fused_bank() : nullptr;
-  if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(idx)) {
+  if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(static_cast<Instrument*>(te)->bank_controls(), idx)) {
     groove_ctl_link* link = nullptr;
     if (!groove_ctl_bank_link_create(ctx_, &desc, 1, bank, (uint32_t)idx, &link)) {
       src->add_link({link, target, (uint32_t)idx, true});
       return 0;
     }
-    // (the library refuses: a bank that is no Welsh bank, a noise LFO — the host path below, with its own checks)
+    // (the library refuses: a noise LFO — the host path below, with its own checks)
   }
   if (desc.source == GROOVE_CTL_SRC_SIGNAL) {
     err_ = "link_control: a signal source onto '" + param + "' would need a download per block (the host derives that parameter's device form); dropped";
@@ -740,14 +741,14 @@ int gh_add_welsh(void* h, const groove_welsh_params* patch, uint32_t voices) {
   std::vector<groove_welsh_params> p(voices, *patch);
   groove_bank* b = nullptr;
   if (groove_welsh_create(o->ctx(), p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
-  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, voices, true, patch->amp_envelope.release, false)));
+  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::WELSH, voices, true, patch->amp_envelope.release, false)));
 }
 int gh_add_fm(void* h, const groove_fm_params* patch, uint32_t voices) {
   Orchestrator* o = (Orchestrator*)h;
   std::vector<groove_fm_params> p(voices, *patch);
   groove_bank* b = nullptr;
   if (groove_fm_create(o->ctx(), p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
-  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, voices, true, patch->carrier_envelope.release, false)));
+  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::FM, voices, true, patch->carrier_envelope.release, false)));
 }
 // Drumkit: one one-shot voice per sample buffer; MIDI key k plays buffer key_to_sample[k] (-1: none).
 int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc,
@@ -770,7 +771,7 @@ int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_samp
     void note_on(uint8_t key, uint8_t vel, uint64_t) override { groove_note_event e{key, key, vel, 1, 0}; groove_bank_note_events(bank(), &e, 1); }
     void note_off(uint8_t, uint8_t, uint64_t) override {}
   };
-  return (int)o->add(std::unique_ptr<Entity>(new Drumkit(o->ctx(), b, 128, true, 0.0, true)));
+  return (int)o->add(std::unique_ptr<Entity>(new Drumkit(o->ctx(), b, BankControls::SAMPLER, 128, true, 0.0, true)));
 }
 // Sampler (settings/src/instruments.rs:34-37, 81-88): one mono buffer, `voices` voices that step through it at note / root (SURVEY A.10:
 // no interpolation), stopped by their note-off.
@@ -782,7 +783,7 @@ int gh_add_sampler(void* h, const float* pcm, uint64_t frames, double root_hz, u
   for (auto& x : p) { x.sample_index = 0; x.one_shot = 0; x.gain = 1.0f; }
   groove_bank* b = nullptr;
   if (groove_sampler_create(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
-  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, voices, true, 0.0, false)));
+  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::SAMPLER, voices, true, 0.0, false)));
 }
 // ToyInstrument (settings/src/instruments.rs:27-28, 67-70; the reference's own test entity, source absent: docs/DSP_SPEC.md section 7): a
 // sine oscillator at the note's pitch, gated by note-on / note-off, through a Dca — here an FM voice with index 0 and a gate for
@@ -796,7 +797,7 @@ int gh_add_toy_instrument(void* h, double dca_gain, double dca_pan) {
   p.dca_gain = (float)dca_gain; p.dca_pan = (float)dca_pan;
   groove_bank* b = nullptr;
   if (groove_fm_create(o->ctx(), &p, 1, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
-  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, 1, true, 0.0, false)));
+  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::TOY, 1, true, 0.0, false)));
 }
 int gh_add_effect(void* h, uint32_t kind, const groove_fx_params* p) {
   Orchestrator* o = (Orchestrator*)h;

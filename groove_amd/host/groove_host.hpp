@@ -80,19 +80,45 @@ inline int fx_control_index_for_name(const std::string& name) {
   for (auto& t : table) if (name == t.first) return t.second;
   return -1;
 }
-// The same for the controls the library's banks expose: WelshSynth's `dca` field gives dca-gain / dca-pan; the filter's cutoff is the one
-// Welsh voice parameter the reference's demos automate on effects.
-inline int bank_control_index_for_name(const std::string& name) {
-  static const std::pair<const char*, int> table[] = {
+// The same for the controls the library's banks expose, per kind of bank (include/groove_types.h: each kind has its own indices).
+//   Welsh: the `dca` field gives dca-gain / dca-pan; the filter's cutoff is the one Welsh voice parameter the reference's demos automate
+//   on effects.  FM: dca-gain / dca-pan, depth and beta (`ratio` has no law and no control).  Sampler and drumkit: gain.  Toy: the
+//   ToyInstrument is an FM bank of one voice behind a Dca — its gain and pan, as before (through groove_bank_set_param, which serves its
+//   bank now; a deliberate exception to `anything else: -1`).  Anything else: -1.
+enum class BankControls { NONE, WELSH, FM, SAMPLER, TOY };
+inline int bank_control_index_for_name(BankControls kind, const std::string& name) {
+  static const std::pair<const char*, int> welsh[] = {
       {"dca-gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"gain", GROOVE_CTL_WELSH_DCA_GAIN}, {"dca-pan", GROOVE_CTL_WELSH_DCA_PAN}, {"pan", GROOVE_CTL_WELSH_DCA_PAN},
       {"filter-cutoff", GROOVE_CTL_WELSH_CUTOFF}, {"cutoff", GROOVE_CTL_WELSH_CUTOFF}};
-  for (auto& t : table) if (name == t.first) return t.second;
-  return -1;
+  static const std::pair<const char*, int> fm[] = {
+      {"dca-gain", GROOVE_CTL_FM_DCA_GAIN}, {"gain", GROOVE_CTL_FM_DCA_GAIN}, {"dca-pan", GROOVE_CTL_FM_DCA_PAN}, {"pan", GROOVE_CTL_FM_DCA_PAN},
+      {"depth", GROOVE_CTL_FM_DEPTH}, {"beta", GROOVE_CTL_FM_BETA}};
+  switch (kind) {
+    case BankControls::WELSH: for (auto& t : welsh) if (name == t.first) return t.second; return -1;
+    case BankControls::FM: for (auto& t : fm) if (name == t.first) return t.second; return -1;
+    case BankControls::TOY: for (size_t i = 0; i < 4; ++i) if (name == fm[i].first) return fm[i].second; return -1;
+    case BankControls::SAMPLER: return name == "gain" ? (int)GROOVE_CTL_SAMPLER_GAIN : -1;
+    default: return -1;
+  }
 }
-// The controls of a Welsh synth a BANK link reaches (groove_ctl_bank_link_create / groove_ctl_bank_trip_create, which have the last word: the
-// bank has to be a Welsh one).
-inline bool bank_control_device_linkable(int index) {
-  return index == GROOVE_CTL_WELSH_DCA_GAIN || index == GROOVE_CTL_WELSH_DCA_PAN || index == GROOVE_CTL_WELSH_CUTOFF;
+// ... of a project file's device kind (project.cpp)
+inline BankControls bank_controls_of_device(const std::string& device_kind) {
+  if (device_kind == "welsh" || device_kind == "welsh-raw") return BankControls::WELSH;
+  if (device_kind == "fm-synthesizer") return BankControls::FM;
+  if (device_kind == "drumkit" || device_kind == "sampler") return BankControls::SAMPLER;
+  if (device_kind == "toy-instrument") return BankControls::TOY;
+  return BankControls::NONE;
+}
+// The controls of an instrument a BANK link reaches (groove_ctl_bank_link_create / groove_ctl_bank_trip_create, which have the last word):
+// every control its kind of bank has.  The toy instrument's gain and pan keep the host path: its names resolve because project files use
+// them (tests/test_project_controllers.py), nothing more is built for it.
+inline bool bank_control_device_linkable(BankControls kind, int index) {
+  switch (kind) {
+    case BankControls::WELSH: return index == GROOVE_CTL_WELSH_DCA_GAIN || index == GROOVE_CTL_WELSH_DCA_PAN || index == GROOVE_CTL_WELSH_CUTOFF;
+    case BankControls::FM: return index >= GROOVE_CTL_FM_DCA_GAIN && index <= GROOVE_CTL_FM_BETA;
+    case BankControls::SAMPLER: return index == GROOVE_CTL_SAMPLER_GAIN;
+    default: return false;
+  }
 }
 // Can a control link onto this parameter of this kind of effect stay on the device (groove_ctl_link_create: the parameters whose device
 // form IS the value, on the kind whose kernels read them)?  (A filter's cutoff, q and passband-ripple can too, through a filter link, where
@@ -140,6 +166,7 @@ class Instrument : public Entity {
   // nothing else, such an instrument needs no voice block at all — the orchestrator renders it fused onto the bus
   // (Orchestrator::gather_audio's fast path).
   virtual groove_bank* fused_bank() { return nullptr; }
+  virtual BankControls bank_controls() const { return BankControls::NONE; } // which controls that bank's kind has
   // Controllable (proc-macros/src/control.rs:171-249: generated for EVERY entity, instruments included): a ControlTrip whose target
   // is an instrument drives these (entities/src/controllers/control_trip.rs:184-254).  -1 / 1: no such control.
   virtual int control_index_for_name(const std::string&) const { return -1; }
@@ -174,7 +201,7 @@ class Controller : public Entity {
 // A synth = ONE patch + a voice store (first-idle allocation, A.6); voices summed to 1 lane.
 class VoiceBankInstrument : public Instrument {
  public:
-  VoiceBankInstrument(groove_ctx* ctx, groove_bank* bank, uint32_t voices, bool sum_voices,
+  VoiceBankInstrument(groove_ctx* ctx, groove_bank* bank, BankControls controls, uint32_t voices, bool sum_voices,
                       double release_seconds, bool one_voice_per_key);
   ~VoiceBankInstrument() override;
   uint32_t lanes() const override { return sum_voices_ ? 1 : voices_; }
@@ -190,13 +217,16 @@ class VoiceBankInstrument : public Instrument {
   void note_off(uint8_t key, uint8_t velocity, uint64_t now_frame) override;
   groove_bank* bank() { return bank_; }
   groove_bank* fused_bank() override { return bank_; }
-  // the controls the library's banks expose (include/groove_types.h GROOVE_CTL_WELSH_*; Welsh banks only), for every voice of the synth
+  BankControls bank_controls() const override { return controls_; }
+  // the controls the library's banks expose (include/groove_types.h GROOVE_CTL_WELSH_*, _FM_*, _SAMPLER_GAIN: by kind of bank), for every
+  // voice of the instrument
   int control_index_for_name(const std::string& name) const override;
   int control_set_param(uint32_t index, double value01) override;
   uint32_t last_allocated_voice() const { return last_voice_; }
  private:
   groove_ctx* ctx_;
   groove_bank* bank_;
+  BankControls controls_;
   uint32_t voices_;
   bool sum_voices_;
   double release_seconds_;
@@ -439,7 +469,8 @@ class Orchestrator {
   int set_wet_reverb_run(bool on);
   bool wet_reverb_run() const;
   bool trips_on_device() const { return trips_on_device_; }
-  // Controls onto a Welsh synth's dca-gain / gain, dca-pan / pan or filter-cutoff / cutoff stay on the device (groove_ctl_bank_trip_create,
+  // Controls onto a Welsh synth's dca-gain / gain, dca-pan / pan or filter-cutoff / cutoff — and onto an FM synth's gain, pan, depth or beta
+  // and a sampler's or drumkit's gain (bank_control_device_linkable) — stay on the device (groove_ctl_bank_trip_create,
   // groove_ctl_bank_link_create): no groove_bank_set_param — a re-derivation, a re-plan and a re-upload of the bank, with their host waits —
   // per automated block.  Off by default and independent of set_trips_on_device.  Trips are placed when a performance starts
   // (skip_to_start), by the effects' rule per instrument: if ANY control reaches the instrument through the host — a parameter or a bank

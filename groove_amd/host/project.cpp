@@ -430,7 +430,7 @@ ProjectDesc parse_project(const std::string& text, const std::string& assets_roo
       const ProjectDesc::Device* dst = nullptr;
       for (const auto& d : p.devices) if (d.id == c.target) dst = &d;
       if (!dst) { p.warnings.push_back("control " + c.id + " controls nonexistent device " + c.target); continue; }
-      const int idx = dst->is_effect ? fx_control_index_for_name(c.param) : bank_control_index_for_name(c.param);
+      const int idx = dst->is_effect ? fx_control_index_for_name(c.param) : bank_control_index_for_name(bank_controls_of_device(dst->kind), c.param);
       if (idx < 0) { p.warnings.push_back("control " + c.id + ": " + c.target + " has no parameter '" + c.param + "'"); continue; }
       if (dst->is_effect && dst->fx_kind != GROOVE_FX_MIXER && fx_control_device_linkable(dst->fx_kind, idx)) c.route = ProjectDesc::CONTROL_ON_DEVICE;
       else if (src->kind == "lfo") c.route = ProjectDesc::CONTROL_PER_BLOCK;

@@ -104,8 +104,9 @@ class Orchestrator:
         self.L.gh_set_trips_on_device(self.h, 1 if on else 0)
 
     def set_instrument_controls_on_device(self, on):
-        """Control trips and LFO `controls` links onto a Welsh synth's dca-gain, dca-pan or filter-cutoff stay on the device (no re-upload
-        of the synth's bank, and no host wait, per automated block).  Trips are decided when a run starts — control_trip_on_device(uid)
+        """Control trips and LFO `controls` links onto an instrument's controls — a Welsh synth's dca-gain, dca-pan or filter-cutoff, an
+        FM synth's dca-gain, dca-pan, depth or beta, a sampler's or drumkit's gain — stay on the device (no re-upload of the instrument's
+        bank, and no host wait, per automated block).  Trips are decided when a run starts — control_trip_on_device(uid)
         says how it went — LFO links when they are made, so set it before link_control.  Off by default; independent of
         set_trips_on_device."""
         self.L.gh_set_instrument_controls_on_device(self.h, 1 if on else 0)

@@ -179,7 +179,11 @@ uint32_t groove_bank_voices(groove_bank* bank);
  * settings/src/patches.rs:928, 821).  Applied in order, at the start of the next render. */
 int groove_bank_note_events(groove_bank* bank, const groove_note_event* ev, uint32_t n_ev);
 /* Controllable::control_set_param_by_index (proc-macros/src/control.rs:211-226); value01 is a
- * ControlValue in 0..1 (orchestration/src/lib.rs:43-47).  voice = GROOVE_ALL_VOICES for all. */
+ * ControlValue in 0..1 (orchestration/src/lib.rs:43-47).  voice = GROOVE_ALL_VOICES for all.
+ * Each bank kind has its own indices (groove_types.h): a Welsh bank GROOVE_CTL_WELSH_* (32 - 34), an FM bank GROOVE_CTL_FM_* (48 - 51:
+ * dca-gain, dca-pan, depth, beta; `ratio` has no control), a sampler or drumkit bank GROOVE_CTL_SAMPLER_GAIN (64).  An index of another
+ * kind is refused with a message that names the kind's own.  The host's copy of the voice's parameters is updated, the ctx stream is
+ * joined and waited for, and the derived parameter records are uploaded again; the voices' state stays where it is. */
 int groove_bank_set_param(groove_bank* bank, uint32_t voice, uint32_t control_index, double value01);
 /* Ticks::tick(frames) + Generates::generate_batch_values: fills out[2][frames][n]. */
 int groove_bank_render(groove_bank* bank, uint32_t frames, groove_block* out);
@@ -385,7 +389,7 @@ int groove_ctl_trip_apply(groove_ctl_link* link, uint64_t at_units);
  * the per-virtual-wave copies.  No host wait, no copy.
  *   src[1] / steps[1][n_steps], start_beat[1]: ONE source, broadcast to every voice (what GROOVE_ALL_VOICES does).  n_src != 1 is
  *   refused: per-voice values would break the wave-uniform parameter records; per-voice changes keep groove_bank_set_param.
- *   control_index: GROOVE_CTL_WELSH_DCA_GAIN, _DCA_PAN or _CUTOFF on a Welsh bank.  Refused: any other index, FM and sampler banks,
+ *   control_index: GROOVE_CTL_WELSH_DCA_GAIN, _DCA_PAN or _CUTOFF on a Welsh bank (FM and sampler banks: below).  Refused: any other index,
  *   a bank that is not live, and whatever groove_ctl_link_create / groove_ctl_trip_create refuse of their sources and steps.
  * Gain and pan share two words, so the bank gets a per-voice (gain, pan) shadow on the device with its first gain or pan link;
  * groove_bank_set_param, a sample-rate change and a reset refresh it from the host's copy.  The staleness rule of the effect links
@@ -401,6 +405,17 @@ int groove_ctl_trip_apply(groove_ctl_link* link, uint64_t at_units);
  * events; it is a between-blocks change like a note event.  A signal link's capture block has one lane.  (The compiled host layer
  * does not make signal links onto instruments: in its render-ahead walk the instruments of block b + 1 render before block b's
  * effects have captured anything, so "the value captured in the previous tick" does not exist there.)
+ * FM and sampler banks: the same two creates take GROOVE_CTL_FM_DCA_GAIN, _DCA_PAN, _DEPTH and _BETA on an FM bank and
+ * GROOVE_CTL_SAMPLER_GAIN on a sampler or drumkit bank, by groove_bank_set_param's laws for those kinds (gain and pan as above; depth,
+ * beta and a sampler's gain: clamp01(v) rounded to float).  Every FM and sampler kernel loads its record from the per-voice parameter
+ * array alone — no per-wave copies, nothing wave-uniform — so here n_src may be 1 (broadcast) OR the bank's voice count: one source
+ * lane per voice, the natural form for a drumkit, where a voice is a drum.  The apply is one thread per voice.  An FM bank gets a
+ * per-voice shadow of (gain, pan, depth, beta) with its first link: gl and gr come from gain and pan, the modulation index
+ * depth * beta — an f64 held in two 32-bit rows of the array — from depth and beta, and each apply writes its own word and reads its
+ * partner.  groove_bank_set_param, a sample-rate change and a reset upload shadow and records again from the host's copy; so
+ * groove_bank_reset of an FM bank that has a link waits on the host for that upload, which a reset of any other bank does not.  A
+ * sampler's gain is one word and needs no shadow: a reset leaves its records as they are, the link's last value included.  The staleness rule and the ordering are the ones above.  A Welsh index on these
+ * banks, an FM index on a sampler bank and the reverse are refused, each with its message.
  * The link returned is an ordinary one: capture, apply / trip apply, reset and destroy under their own rules.  groove_bank_destroy
  * leaves it without a target: its next apply is an error. */
 int groove_ctl_bank_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_bank* target, uint32_t control_index,

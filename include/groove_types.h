@@ -186,7 +186,15 @@ typedef enum {
   GROOVE_CTL_FX_THRESHOLD = 7,       /* "threshold" (Compressor; the reference's compressor demo ramps it) */
   GROOVE_CTL_WELSH_DCA_GAIN = 32,    /* "dca-gain"         */
   GROOVE_CTL_WELSH_DCA_PAN = 33,     /* "dca-pan"          */
-  GROOVE_CTL_WELSH_CUTOFF = 34       /* "filter-cutoff" (value01 → Hz) */
+  GROOVE_CTL_WELSH_CUTOFF = 34,      /* "filter-cutoff" (value01 → Hz) */
+  /* FM banks (FmSynthParams, settings/src/patches.rs:691-715).  `ratio` has no control: patches.rs:694 itself says it still needs a
+   * type, and no law for it exists anywhere in the reference tree. */
+  GROOVE_CTL_FM_DCA_GAIN = 48,       /* "dca-gain" / "gain": the Welsh law               */
+  GROOVE_CTL_FM_DCA_PAN = 49,        /* "dca-pan" / "pan": the Welsh law                 */
+  GROOVE_CTL_FM_DEPTH = 50,          /* "depth": (float)clamp01(v), a Normal             */
+  GROOVE_CTL_FM_BETA = 51,           /* "beta": (float)clamp01(v), set_beta(value.into()) */
+  /* sampler and drumkit banks */
+  GROOVE_CTL_SAMPLER_GAIN = 64       /* "gain": (float)clamp01(v)                        */
 } groove_control_index;
 
 /* Controller devices (the schema's third device class, settings/src/controllers.rs: "lfo", "signal-passthrough-controller")
