@@ -1389,6 +1389,43 @@ GROOVE_HD void sampler_chunk(const SamplerParams& p, SamplerState& s, const floa
   if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
 }
 
+// A STEREO bank (groove_sampler_create_stereo): a left and a right value per frame, interleaved, so that both channels of a frame
+// arrive with ONE 8-byte fetch; index, end and note rules are the mono ones word for word, and the state record is the same.
+struct alignas(8) SamplePair { float l, r; }; // (8-byte aligned: the bank is the library's own allocation)
+static_assert(sizeof(SamplePair) == 8, "a frame of a stereo bank is two adjacent floats");
+GROOVE_HD void sampler_frame_stereo(const SamplerParams& p, SamplerState& s, const SamplePair* bank, float& L, float& R) {
+  L = R = 0.0f;
+  if (!s.playing) return;
+  const uint32_t i = (uint32_t)(s.idx >> 44);
+  if (i >= p.length) { s.playing = 0; return; }
+  const SamplePair t = bank[(size_t)p.offset + i];
+  L = t.l * p.gain;
+  R = t.r * p.gain;
+  s.idx += s.step;
+}
+// sampler_chunk for a stereo bank: all C fetches (both channels each) issued from clamped addresses before any is used.
+template <int C>
+GROOVE_HD void sampler_chunk_stereo(const SamplerParams& p, SamplerState& s, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) {
+  uint32_t valid = 0; // frames of the chunk that play
+  SamplePair raw[C];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint32_t i = (uint32_t)((s.idx + (uint64_t)k * s.step) >> 44);
+    const bool ok = s.playing && (uint32_t)k < count && i < p.length;
+    raw[k] = bank[(size_t)p.offset + (i < p.length ? i : p.length - 1)];
+    valid += ok ? 1u : 0u;
+    l[k] = ok ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const bool ok = l[k] != 0.0f;
+    l[k] = ok ? raw[k].l * p.gain : 0.0f;
+    r[k] = ok ? raw[k].r * p.gain : 0.0f;
+  }
+  s.idx += (uint64_t)valid * s.step;
+  if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+}
+
 // ------------------------------------------------------------------ effects (a8, a9)
 GROOVE_HD float bitcrush(float x, uint32_t bits) {
   float ax = fabsf(x) * 32767.0f;

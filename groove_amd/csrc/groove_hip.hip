@@ -125,7 +125,8 @@ struct groove_bank {
   // from entry 0, plan.striped — the mix kernel's sections, [wg_list_cap + mix_off[s], + mix_cnt[s]) — from entry wg_list_cap
   uint32_t* d_wg_list = nullptr;
   size_t wg_list_cap = 0;
-  float* d_pcm = nullptr;   // sampler bank
+  float* d_pcm = nullptr;   // sampler bank: [bank_frames] values, or [bank_frames] interleaved left, right pairs ...
+  bool pcm_stereo = false;  // ... of a stereo bank (groove_sampler_create_stereo): picks the kernels' STEREO instantiations
   // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
   // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
   // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one).  fm: the same owner with CTL_FM_WORDS rows — gain, pan, depth,
@@ -1525,29 +1526,44 @@ int groove_fm_create(groove_ctx* ctx, const groove_fm_params* p, uint32_t n, gro
   if (hipMalloc(&b->d_cold, (size_t)n * 8) != hipSuccess) { delete b; return fail(ctx, "groove_fm_create: hipMalloc failed"); }
   return bank_finish_create(b, out);
 }
-int groove_sampler_create(groove_ctx* ctx, const float* bank_pcm, uint64_t bank_frames,
+// groove_sampler_create (channels 1) and groove_sampler_create_stereo (channels 2: the host's interleaved L, R frames are the device's)
+static int sampler_create(const char* who, uint32_t channels, groove_ctx* ctx, const float* bank_pcm, uint64_t bank_frames,
                           const groove_sample_desc* descs, uint32_t n_samples,
                           const groove_sampler_params* p, uint32_t n, groove_bank** out) {
-  if (!ctx || !bank_pcm || !descs || !p || !out) return fail(ctx, "groove_sampler_create: NULL argument");
-  if (n == 0 || n_samples == 0 || bank_frames == 0) return fail(ctx, "groove_sampler_create: empty bank");
-  if (bank_frames >= (1ull << 32)) return fail(ctx, "groove_sampler_create: bank too large");
+  const std::string w = std::string(who) + ": ";
+  if (!ctx || !bank_pcm || !descs || !p || !out) return fail(ctx, w + "NULL argument");
+  if (n == 0 || n_samples == 0 || bank_frames == 0) return fail(ctx, w + "empty bank");
+  if (bank_frames >= (1ull << 32)) return fail(ctx, w + "bank too large");
   for (uint32_t i = 0; i < n_samples; ++i) {
     if (descs[i].offset > bank_frames || descs[i].length > bank_frames - descs[i].offset)
-      return fail(ctx, "groove_sampler_create: sample descriptor exceeds bank");
-    if (descs[i].length == 0) return fail(ctx, "groove_sampler_create: empty sample"); // the fetch clamps to length - 1
-    if (descs[i].length >= (1u << 20)) return fail(ctx, "groove_sampler_create: sample longer than 2^20 frames");
+      return fail(ctx, w + "sample descriptor exceeds bank");
+    if (descs[i].length == 0) return fail(ctx, w + "empty sample"); // the fetch clamps to length - 1
+    if (descs[i].length >= (1u << 20)) return fail(ctx, w + "sample longer than 2^20 frames");
   }
   for (uint32_t i = 0; i < n; ++i)
-    if (p[i].sample_index >= n_samples) return fail(ctx, "groove_sampler_create: sample_index out of range");
+    if (p[i].sample_index >= n_samples) return fail(ctx, w + "sample_index out of range");
   groove_bank* b = new groove_bank();
   b->ctx = ctx; b->kind = BANK_SAMPLER; b->n = n;
   b->pw = sizeof(SamplerParams) / 4; b->sw = sizeof(SamplerState) / 4;
   b->sampler.assign(p, p + n);
   b->descs.assign(descs, descs + n_samples);
-  if (hipMalloc(&b->d_pcm, bank_frames * 4) != hipSuccess) { delete b; return fail(ctx, "groove_sampler_create: hipMalloc failed"); }
-  if (ctx_memcpy(ctx, b->d_pcm, bank_pcm, bank_frames * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(b->d_pcm); delete b; return fail(ctx, "groove_sampler_create: upload failed"); }
+  b->pcm_stereo = channels == 2;
+  const size_t bytes = (size_t)bank_frames * 4 * channels;
+  if (hipMalloc(&b->d_pcm, bytes) != hipSuccess) { delete b; return fail(ctx, w + "hipMalloc failed"); }
+  if (ctx_memcpy(ctx, b->d_pcm, bank_pcm, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(b->d_pcm); delete b; return fail(ctx, w + "upload failed"); }
   return bank_finish_create(b, out);
 }
+int groove_sampler_create(groove_ctx* ctx, const float* bank_pcm, uint64_t bank_frames,
+                          const groove_sample_desc* descs, uint32_t n_samples,
+                          const groove_sampler_params* p, uint32_t n, groove_bank** out) {
+  return sampler_create("groove_sampler_create", 1, ctx, bank_pcm, bank_frames, descs, n_samples, p, n, out);
+}
+int groove_sampler_create_stereo(groove_ctx* ctx, const float* bank_pcm_lr, uint64_t bank_frames,
+                                 const groove_sample_desc* descs, uint32_t n_samples,
+                                 const groove_sampler_params* p, uint32_t n, groove_bank** out) {
+  return sampler_create("groove_sampler_create_stereo", 2, ctx, bank_pcm_lr, bank_frames, descs, n_samples, p, n, out);
+}
+uint32_t groove_bank_sample_channels(groove_bank* b) { return b && b->kind == BANK_SAMPLER ? (b->pcm_stereo ? 2u : 1u) : 0u; }
 int groove_bank_destroy(groove_bank* b) {
   if (!b) return 0;
   groove_ctx* ctx = b->ctx;
@@ -1773,7 +1789,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (prev) a.prev = *prev;
       if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
       if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
-      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
+      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
       else { a.full_coef = b->plan.tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
       break;
     }
@@ -1792,7 +1808,10 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       else launch_bound(fm_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows);
       break;
     case Form::SamplerSerial:
-      if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+      if (b->pcm_stereo) {
+        if (fused) launch_bound(sampler_render_kernel<true, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+        else launch_bound(sampler_render_kernel<false, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+      } else if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
       else launch_bound(sampler_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
       break;
     case Form::WelshBigUniform: break; // (the callers' own walks over big_pieces / the base kinds: their stream policies differ on purpose)
@@ -2171,7 +2190,7 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
 // groove_bank_render_mix_deferred for SEVERAL small banks of different kinds at once: ONE launch for the whole block (welsh_tp.h
 // tp_mixed_kernel: a grid whose workgroups dispatch on their index into the Welsh / FM / sampler time-parallel bodies), one row
 // buffer, one carried reduction — Orchestrator::gather_audio's one sum over all instruments (orchestrator.rs:397-410).  Takes
-// projects with at most one time-parallel bank of each kind and at most 2,048 rows in all; anything else goes bank by bank
+// projects with at most one time-parallel bank of each kind, no stereo sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
 // through groove_bank_render_mix_deferred, in the order given.
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate) {
   if (!ctx || !bus_dev || (n_banks && !banks)) return fail(ctx, "groove_banks_render_mix_deferred: NULL argument");
@@ -2188,7 +2207,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
     if (!b) return fail(ctx, "groove_banks_render_mix_deferred: NULL bank");
     if (b->ctx != ctx) return fail(ctx, "groove_banks_render_mix_deferred: a bank of another ctx");
     const int k = b->kind == BANK_WELSH ? 0 : b->kind == BANK_FM ? 1 : 2;
-    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef)) ok = false;
+    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo) ok = false; // (tp_mixed_kernel's sampler body is the mono one)
     of_kind[k] = b;
   }
   TpMixedArgs m{};

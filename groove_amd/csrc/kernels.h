@@ -870,8 +870,9 @@ __global__ __launch_bounds__(kThreads) void fm_render_kernel(
   if (active) soa_store(state, n, v, s);
 }
 
-// a7 SamplerVoice: pointer stepping; the shared bank is a gather served from L2 / MALL.
-template <bool FUSED>
+// a7 SamplerVoice: pointer stepping; the shared bank is a gather served from L2 / MALL.  STEREO: `bank` holds interleaved left, right
+// frames (dsp_core.h SamplePair; one 8-byte fetch per frame), and the two channels are two values all the way to the bus.
+template <bool FUSED, bool STEREO = false>
 __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n, uint32_t frames,
     size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank) {
@@ -887,12 +888,15 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
   for (uint32_t f0 = 0; f0 < frames; f0 += C) {
     const uint32_t count = min(C, frames - f0);
     float x[C];
-    sampler_chunk<C>(p, s, bank, count, x);
+    float xr[STEREO ? C : 1]; // (a stereo bank's right channel; a mono voice is duplicated to both channels)
+    if constexpr (STEREO) sampler_chunk_stereo<C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
+    else sampler_chunk<C>(p, s, bank, count, x);
 #pragma unroll
     for (uint32_t k = 0; k < C; ++k) {
       if (k < count) {
-        acc.add(active ? x[k] : 0.0f, active ? x[k] : 0.0f, f0 + k);
-        if (!FUSED && active) { out[(size_t)(f0 + k) * n + v] = x[k]; out[ch_stride + (size_t)(f0 + k) * n + v] = x[k]; }
+        const float r = STEREO ? xr[STEREO ? k : 0] : x[k];
+        acc.add(active ? x[k] : 0.0f, active ? r : 0.0f, f0 + k);
+        if (!FUSED && active) { out[(size_t)(f0 + k) * n + v] = x[k]; out[ch_stride + (size_t)(f0 + k) * n + v] = r; }
       }
       if ((k & (K - 1)) == K - 1 && k - (K - 1) < count) acc.flush(rows, frames, f0 + k - (K - 1), min(K, count - (k - (K - 1))));
     }

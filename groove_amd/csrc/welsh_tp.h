@@ -861,13 +861,20 @@ inline uint32_t sampler_tp_workgroups(uint32_t n, uint32_t vpw = 0) { const uint
 // groove_bank_render_mix_deferred: no reduction launch to keep short, so the voices are spread over the chip — at most 512 rows
 // (config #4: 4 voices per wavefront, 256 workgroups on 256 CUs instead of 64 on 64)
 inline uint32_t sampler_tp_vpw_deferred(uint32_t n) { return n <= 1024 ? 1u : std::min<uint32_t>((n + 8191) / 8192 * 2, 16u); }
-template <int WAVES> struct SamplerTpSmem {
+template <int WAVES, bool STEREO = false> struct SamplerTpSmem {
   float tile[WAVES][kTpMaxFrames];
   volatile uint32_t ev[WAVES][64]; // volatile: lanes read what OTHER lanes of the wave wrote, with no barrier the compiler knows of
 };
+template <int WAVES> struct SamplerTpSmem<WAVES, true> { // a stereo bank: the left sums' tile and the right sums'
+  float tile[WAVES][kTpMaxFrames];
+  float tile_r[WAVES][kTpMaxFrames];
+  volatile uint32_t ev[WAVES][64];
+};
 // WAVES wavefronts per workgroup: 16 in the bank's own kernel, 4 in the mixed kernel (whose workgroups are 256 threads)
-template <bool FUSED, int WAVES>
-__device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES>& sm) {
+// STEREO: `bank` holds interleaved left, right frames (dsp_core.h SamplePair): one 8-byte fetch per frame, two accumulators per frame,
+// two tiles; each channel's sum is taken in the order the mono sum is (voice order within a wave, wave order within the workgroup).
+template <bool FUSED, int WAVES, bool STEREO = false>
+__device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES, STEREO>& sm) {
   float (&s_tile)[WAVES][kTpMaxFrames] = sm.tile;
   volatile uint32_t (&s_ev)[WAVES][64] = sm.ev;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -907,8 +914,9 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
   }
   const uint32_t n0 = lane * kTpChunk;
   float acc[kTpChunk];
+  float acc_r[STEREO ? kTpChunk : 1];
 #pragma unroll
-  for (uint32_t j = 0; j < kTpChunk; ++j) acc[j] = 0.0f;
+  for (uint32_t j = 0; j < kTpChunk; ++j) { acc[j] = 0.0f; if constexpr (STEREO) acc_r[j] = 0.0f; }
   const uint32_t idx_lo = (uint32_t)s0.idx, idx_hi = (uint32_t)(s0.idx >> 32), step_lo = (uint32_t)s0.step, step_hi = (uint32_t)(s0.step >> 32);
   constexpr uint32_t U = 4; // voices whose fetches are issued together
   for (uint32_t k0 = 0; k0 < cnt; k0 += U) { // k is wave-uniform: v_readlane
@@ -929,6 +937,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     }
     if (!any) continue; // (uniform)
     float raw[U][kTpChunk];
+    float raw_r[STEREO ? U : 1][STEREO ? kTpChunk : 1];
     bool ok[U][kTpChunk];
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
@@ -937,22 +946,31 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
         const uint32_t f = n0 + j;
         const uint32_t i = (uint32_t)((idx[u] + (uint64_t)f * step[u]) >> 44);
         ok[u][j] = playing[u] && f < frames && i < len[u];
-        raw[u][j] = bank[(size_t)off[u] + (i < len[u] ? i : len[u] - 1)];
+        if constexpr (STEREO) {
+          const SamplePair t = reinterpret_cast<const SamplePair*>(bank)[(size_t)off[u] + (i < len[u] ? i : len[u] - 1)];
+          raw[u][j] = t.l; raw_r[u][j] = t.r;
+        } else {
+          raw[u][j] = bank[(size_t)off[u] + (i < len[u] ? i : len[u] - 1)];
+        }
       }
     }
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) { // accumulated voice by voice, in voice order
       if (!playing[u]) continue;
       float x[kTpChunk];
+      float x_r[STEREO ? kTpChunk : 1];
 #pragma unroll
-      for (uint32_t j = 0; j < kTpChunk; ++j) { x[j] = ok[u][j] ? raw[u][j] * gain[u] : 0.0f; acc[j] += x[j]; }
+      for (uint32_t j = 0; j < kTpChunk; ++j) {
+        x[j] = ok[u][j] ? raw[u][j] * gain[u] : 0.0f; acc[j] += x[j];
+        if constexpr (STEREO) { x_r[j] = ok[u][j] ? raw_r[u][j] * gain[u] : 0.0f; acc_r[j] += x_r[j]; }
+      }
       if (!FUSED) {
         const uint32_t vk = v_begin + k0 + u;
 #pragma unroll
         for (uint32_t j = 0; j < kTpChunk; ++j) {
           if (n0 + j < frames) {
             a.out[(size_t)(n0 + j) * n + vk] = x[j];
-            a.out[a.ch_stride + (size_t)(n0 + j) * n + vk] = x[j];
+            a.out[a.ch_stride + (size_t)(n0 + j) * n + vk] = STEREO ? x_r[STEREO ? j : 0] : x[j];
           }
         }
       }
@@ -969,14 +987,21 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     }
   }
 #pragma unroll
-  for (uint32_t j = 0; j < kTpChunk; ++j) s_tile[wave][n0 + j] = acc[j];
+  for (uint32_t j = 0; j < kTpChunk; ++j) { s_tile[wave][n0 + j] = acc[j]; if constexpr (STEREO) sm.tile_r[wave][n0 + j] = acc_r[j]; }
   __syncthreads();
   for (uint32_t t = threadIdx.x; t < frames; t += WAVES * 64) {
     float sum = 0.0f;
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) sum += s_tile[w][t];
     a.rows[((size_t)g.row * 2 + 0) * frames + t] = sum; // mono voices: the same sum on both channels
-    a.rows[((size_t)g.row * 2 + 1) * frames + t] = sum;
+    if constexpr (STEREO) {
+      float sum_r = 0.0f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) sum_r += sm.tile_r[w][t];
+      a.rows[((size_t)g.row * 2 + 1) * frames + t] = sum_r;
+    } else {
+      a.rows[((size_t)g.row * 2 + 1) * frames + t] = sum;
+    }
   }
   if (mine && frames) {
     SamplerState s = s0;
@@ -985,10 +1010,10 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     soa_store(a.state, n, v, s);
   }
 }
-template <bool FUSED>
+template <bool FUSED, bool STEREO = false>
 __global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw) {
-  __shared__ SamplerTpSmem<kSamplerTpWaves> sm;
-  sampler_tp_body<FUSED, kSamplerTpWaves>(a, bank, ie, vpw, tp_wg_own(), sm);
+  __shared__ SamplerTpSmem<kSamplerTpWaves, STEREO> sm;
+  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO>(a, bank, ie, vpw, tp_wg_own(), sm);
 }
 // ------------------------------------------------------------------ several small banks in ONE launch (round 5)
 // A project of a few small banks of different kinds (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096
@@ -1034,7 +1059,7 @@ inline uint32_t mixed_sampler_workgroups(uint32_t n, uint32_t vpw) { const uint3
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done = nullptr); // welsh.vpw 1 | 2, fm.vpw 1 | 4
 void launch_welsh_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.bq_coef set (block-writing form): the BiQuad head fused; done: an event bound to the dispatch
 void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.vpw voices per wavefront (1, 2, 4)
-void launch_sampler_tp(const TpArgs& a, const float* bank, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr);
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames
 inline uint32_t welsh_tp_workgroups(uint32_t n, uint32_t vpw = 1) { return (n + kTpWaves * vpw - 1) / (kTpWaves * vpw); } // FM: groups of 4 vpw voices per workgroup, plain order
 inline uint32_t welsh_tp_grid(uint32_t n, uint32_t vpw = 1) { // Welsh: padded for the XCD-aware mapping (idle workgroups write zero rows)
   const uint32_t g = welsh_tp_workgroups(n, vpw);

@@ -42,10 +42,13 @@ void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done) 
   else if (a.vpw == 2) launch_fm_tp_vpw<2>(a, st, fused, done);
   else launch_fm_tp_vpw<1>(a, st, fused, done);
 }
-void launch_sampler_tp(const TpArgs& a, const float* bank, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
   const uint32_t vpw = a.vpw > 1 ? a.vpw : sampler_tp_vpw(a.n); // (a.vpw: the deferred form's choice)
   const dim3 grid(sampler_tp_workgroups(a.n, vpw)), blk(kSamplerTpThreads);
-  if (fused) launch_bound(sampler_tp_kernel<true>, grid, blk, st, done, a, bank, ie, vpw);
+  if (stereo) {
+    if (fused) launch_bound(sampler_tp_kernel<true, true>, grid, blk, st, done, a, bank, ie, vpw);
+    else launch_bound(sampler_tp_kernel<false, true>, grid, blk, st, done, a, bank, ie, vpw);
+  } else if (fused) launch_bound(sampler_tp_kernel<true>, grid, blk, st, done, a, bank, ie, vpw);
   else launch_bound(sampler_tp_kernel<false>, grid, blk, st, done, a, bank, ie, vpw);
 }
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done) {

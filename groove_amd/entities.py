@@ -393,14 +393,22 @@ class FmSynth(Instrument):
 
 
 class Sampler(Instrument):
-    """Sampler / Drumkit over a shared mono sample bank.  Controllable: abi_types.CTL_SAMPLER_GAIN."""
+    """Sampler / Drumkit over a shared sample bank: `pcm` of shape [frames] is a mono bank, [frames, 2] a stereo one (left, right per
+    frame; descs stay in frames).  Controllable: abi_types.CTL_SAMPLER_GAIN."""
 
     def __init__(self, ctx, pcm, descs, params):
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 2 and pcm.shape[1] != 2:
+            raise ValueError(f"Sampler: a stereo bank is [frames, 2], not {pcm.shape}")
+        create = ctx.L.groove_sampler_create_stereo if pcm.ndim == 2 else ctx.L.groove_sampler_create
         h = C.c_void_p()
-        _lib.check(ctx.L.groove_sampler_create(ctx.h, pcm.ctypes.data_as(_fp), pcm.size, descs, len(descs),
-                                               params, len(params), C.byref(h)), ctx.h)
+        _lib.check(create(ctx.h, pcm.ctypes.data_as(_fp), pcm.shape[0], descs, len(descs), params, len(params), C.byref(h)), ctx.h)
         super().__init__(ctx, h, len(params))
+
+    @property
+    def sample_channels(self):
+        """groove_bank_sample_channels: 1 (mono bank) or 2 (stereo bank)."""
+        return self.ctx.L.groove_bank_sample_channels(self.h)
 
 
 class Effect:

@@ -750,9 +750,10 @@ int gh_add_fm(void* h, const groove_fm_params* patch, uint32_t voices) {
   if (groove_fm_create(o->ctx(), p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
   return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::FM, voices, true, patch->carrier_envelope.release, false)));
 }
-// Drumkit: one one-shot voice per sample buffer; MIDI key k plays buffer key_to_sample[k] (-1: none).
-int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc,
-                   const int* key_to_sample /*[128]*/) {
+// Drumkit: one one-shot voice per sample buffer; MIDI key k plays buffer key_to_sample[k] (-1: none).  stereo: pcm is [frames][2],
+// interleaved left, right (groove_sampler_create_stereo).
+static int add_drumkit(void* h, bool stereo, const float* pcm, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc,
+                       const int* key_to_sample /*[128]*/) {
   Orchestrator* o = (Orchestrator*)h;
   // voice v plays the sample mapped from key v, so that note_on(key) drives voice `key`
   std::vector<groove_sampler_params> p(128);
@@ -765,7 +766,8 @@ int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_samp
   }
   for (auto& x : d) x.root_hz = 0.0f; // drumkit: step 1 regardless of key
   groove_bank* b = nullptr;
-  if (groove_sampler_create(o->ctx(), pcm, frames, d.data(), n_desc, p.data(), 128, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
+  if (stereo ? groove_sampler_create_stereo(o->ctx(), pcm, frames, d.data(), n_desc, p.data(), 128, &b)
+             : groove_sampler_create(o->ctx(), pcm, frames, d.data(), n_desc, p.data(), 128, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
   struct Drumkit : VoiceBankInstrument {
     using VoiceBankInstrument::VoiceBankInstrument;
     void note_on(uint8_t key, uint8_t vel, uint64_t) override { groove_note_event e{key, key, vel, 1, 0}; groove_bank_note_events(bank(), &e, 1); }
@@ -773,18 +775,27 @@ int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_samp
   };
   return (int)o->add(std::unique_ptr<Entity>(new Drumkit(o->ctx(), b, BankControls::SAMPLER, 128, true, 0.0, true)));
 }
-// Sampler (settings/src/instruments.rs:34-37, 81-88): one mono buffer, `voices` voices that step through it at note / root (SURVEY A.10:
-// no interpolation), stopped by their note-off.
-int gh_add_sampler(void* h, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) {
+int gh_add_drumkit(void* h, const float* pcm, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc, const int* key_to_sample /*[128]*/) {
+  return add_drumkit(h, false, pcm, frames, descs, n_desc, key_to_sample);
+}
+int gh_add_drumkit_stereo(void* h, const float* pcm_lr, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc, const int* key_to_sample /*[128]*/) {
+  return add_drumkit(h, true, pcm_lr, frames, descs, n_desc, key_to_sample);
+}
+// Sampler (settings/src/instruments.rs:34-37, 81-88): one buffer (mono, or stereo: [frames][2] interleaved), `voices` voices that step
+// through it at note / root (no interpolation), stopped by their note-off.
+static int add_sampler(void* h, bool stereo, const char* who, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) {
   Orchestrator* o = (Orchestrator*)h;
-  if (!pcm || !frames || !voices) { o->fail("gh_add_sampler: empty sample"); return -1; }
+  if (!pcm || !frames || !voices) { o->fail(std::string(who) + ": empty sample"); return -1; }
   groove_sample_desc d{0, (uint32_t)std::min<uint64_t>(frames, 0xFFFFFFFFu), (float)root_hz};
   std::vector<groove_sampler_params> p(voices);
   for (auto& x : p) { x.sample_index = 0; x.one_shot = 0; x.gain = 1.0f; }
   groove_bank* b = nullptr;
-  if (groove_sampler_create(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
+  if (stereo ? groove_sampler_create_stereo(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)
+             : groove_sampler_create(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
   return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::SAMPLER, voices, true, 0.0, false)));
 }
+int gh_add_sampler(void* h, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) { return add_sampler(h, false, "gh_add_sampler", pcm, frames, root_hz, voices); }
+int gh_add_sampler_stereo(void* h, const float* pcm_lr, uint64_t frames, double root_hz, uint32_t voices) { return add_sampler(h, true, "gh_add_sampler_stereo", pcm_lr, frames, root_hz, voices); }
 // ToyInstrument (settings/src/instruments.rs:27-28, 67-70; the reference's own test entity, source absent: docs/DSP_SPEC.md section 7): a
 // sine oscillator at the note's pitch, gated by note-on / note-off, through a Dca — here an FM voice with index 0 and a gate for
 // an envelope; `fake-value` is a dummy control of the reference's tests and has no sound.
@@ -825,6 +836,8 @@ void gh_set_filter_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_fi
 void gh_set_trips_on_device(void* h, int on) { ((Orchestrator*)h)->set_trips_on_device(on != 0); }
 void gh_set_wet_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_wet_links_on_device(on != 0); }
 int gh_wet_links_on_device(void* h) { return ((Orchestrator*)h)->wet_links_on_device() ? 1 : 0; }
+void gh_set_stereo_samples(void* h, int on) { ((Orchestrator*)h)->set_stereo_samples(on != 0); }
+int gh_stereo_samples(void* h) { return ((Orchestrator*)h)->stereo_samples() ? 1 : 0; }
 int gh_set_wet_reverb_run(void* h, int on) { return ((Orchestrator*)h)->set_wet_reverb_run(on != 0); }
 int gh_wet_reverb_run(void* h) { return ((Orchestrator*)h)->wet_reverb_run() ? 1 : 0; }
 void gh_set_instrument_controls_on_device(void* h, int on) { ((Orchestrator*)h)->set_instrument_controls_on_device(on != 0); }

@@ -481,6 +481,10 @@ class Orchestrator {
   // "value captured in the previous tick" cannot be honoured there (the library call takes signal sources; the host layer does not use it).
   void set_instrument_controls_on_device(bool on) { instrument_controls_on_device_ = on; }
   bool instrument_controls_on_device() const { return instrument_controls_on_device_; }
+  // Samplers and drumkits keep the channels of two-channel sample files (groove_sampler_create_stereo) instead of averaging them before
+  // upload.  Read when a project is instantiated (project.hpp instantiate).  Off by default: a stereo file is then the mean of its channels.
+  void set_stereo_samples(bool on) { stereo_samples_ = on; }
+  bool stereo_samples() const { return stereo_samples_; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -527,6 +531,7 @@ class Orchestrator {
   bool trips_on_device_ = false;
   bool wet_links_on_device_ = false;
   bool instrument_controls_on_device_ = false;
+  bool stereo_samples_ = false;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block

@@ -451,7 +451,8 @@ ProjectDesc parse_project_file(const std::string& path, const std::string& asset
   return p;
 }
 
-std::string describe(const ProjectDesc& p) {
+namespace { std::string find_sample_file(const std::string& name, const std::string& assets_root, const std::string& project_dir); }
+std::string describe(const ProjectDesc& p, const std::string& assets_root, bool stereo_samples) {
   std::ostringstream o;
   o.precision(10);
   o << "{\"title\":\"" << p.title << "\",\"bpm\":" << p.bpm << ",\"time_signature\":[" << p.ts_top << "," << p.ts_bottom << "],\"devices\":[";
@@ -461,7 +462,14 @@ std::string describe(const ProjectDesc& p) {
       << ",\"midi_in\":" << d.midi_in << ",\"name\":\"" << d.name << "\",\"fx_kind\":" << d.fx_kind << ",\"cutoff\":" << d.fx.cutoff_hz
       << ",\"passband_ripple\":" << d.fx.passband_ripple << ",\"welsh_osc1\":" << d.welsh.oscillator_1.waveform
       << ",\"welsh_mix\":" << d.welsh.oscillator_mix << ",\"welsh_cutoff\":" << d.welsh.filter_cutoff_hz
-      << ",\"welsh_release\":" << d.welsh.amp_envelope.release << ",\"welsh_routing\":" << d.welsh.lfo_routing << "}";
+      << ",\"welsh_release\":" << d.welsh.amp_envelope.release << ",\"welsh_routing\":" << d.welsh.lfo_routing;
+    if (d.kind == "sampler") { // the channels of the bank instantiate() would make (1 where the file cannot be read: instantiate reports that)
+      uint32_t ch = 1;
+      std::vector<float> pcm;
+      if (stereo_samples && !read_wav_stereo(find_sample_file(d.name, assets_root, p.project_dir), pcm, &ch, nullptr, nullptr)) ch = 1;
+      o << ",\"channels\":" << ch;
+    }
+    o << "}";
   }
   o << "],\"patch_cables\":[";
   for (size_t i = 0; i < p.patch_cables.size(); ++i) {
@@ -491,44 +499,73 @@ std::string describe(const ProjectDesc& p) {
   return o.str();
 }
 
-bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* sample_rate, std::string* err) {
+namespace {
+// The one WAV parser: the chunk walk, and the decode of the sample at byte `o` (ints scaled by 2^(bits-1), A.10).
+struct WavData {
   std::string data;
-  try { data = slurp(path); } catch (const std::exception& e) { if (err) *err = e.what(); return false; }
-  auto rd16 = [&](size_t o) { return (uint32_t)(uint8_t)data[o] | ((uint32_t)(uint8_t)data[o + 1] << 8); };
-  auto rd32 = [&](size_t o) { return rd16(o) | (rd16(o + 2) << 16); };
-  if (data.size() < 12 || data.compare(0, 4, "RIFF") != 0 || data.compare(8, 4, "WAVE") != 0) { if (err) *err = "not a RIFF/WAVE file: " + path; return false; }
   uint32_t fmt = 0, channels = 0, rate = 0, bits = 0;
-  size_t pos = 12, dpos = 0, dlen = 0;
+  size_t dpos = 0, frames = 0;
+  uint32_t rd16(size_t o) const { return (uint32_t)(uint8_t)data[o] | ((uint32_t)(uint8_t)data[o + 1] << 8); }
+  uint32_t rd32(size_t o) const { return rd16(o) | (rd16(o + 2) << 16); }
+  double value(size_t f, uint32_t c) const {
+    const size_t bytes = bits / 8, o = dpos + (f * channels + c) * bytes;
+    double v = 0.0;
+    if (fmt == 3 && bits == 32) { float x; std::memcpy(&x, &data[o], 4); v = x; }
+    else if (bits == 16) v = (int16_t)rd16(o) / 32768.0;
+    else if (bits == 24) { int32_t x = (int32_t)(rd16(o) | ((uint32_t)(uint8_t)data[o + 2] << 16)); if (x & 0x800000) x |= ~0xFFFFFF; v = x / 8388608.0; }
+    else if (bits == 32) v = (int32_t)rd32(o) / 2147483648.0;
+    else if (bits == 8) v = ((uint8_t)data[o] - 128) / 128.0;
+    return v;
+  }
+  float mean(size_t f) const { // every channel, in file order
+    double acc = 0.0;
+    for (uint32_t c = 0; c < channels; ++c) acc += value(f, c);
+    return (float)(acc / channels);
+  }
+};
+bool wav_open(const std::string& path, WavData& w, std::string* err) {
+  std::string& data = w.data;
+  try { data = slurp(path); } catch (const std::exception& e) { if (err) *err = e.what(); return false; }
+  if (data.size() < 12 || data.compare(0, 4, "RIFF") != 0 || data.compare(8, 4, "WAVE") != 0) { if (err) *err = "not a RIFF/WAVE file: " + path; return false; }
+  size_t pos = 12, dlen = 0;
   while (pos + 8 <= data.size()) {
     const std::string id = data.substr(pos, 4);
-    const size_t len = rd32(pos + 4);
-    if (id == "fmt " && pos + 8 + 16 <= data.size()) { fmt = rd16(pos + 8); channels = rd16(pos + 10); rate = rd32(pos + 12); bits = rd16(pos + 22);
-      if (fmt == 0xFFFE && len >= 26 && pos + 8 + 26 <= data.size()) fmt = rd16(pos + 8 + 24); }
-    else if (id == "data") { dpos = pos + 8; dlen = std::min(len, data.size() - dpos); }
+    const size_t len = w.rd32(pos + 4);
+    if (id == "fmt " && pos + 8 + 16 <= data.size()) { w.fmt = w.rd16(pos + 8); w.channels = w.rd16(pos + 10); w.rate = w.rd32(pos + 12); w.bits = w.rd16(pos + 22);
+      if (w.fmt == 0xFFFE && len >= 26 && pos + 8 + 26 <= data.size()) w.fmt = w.rd16(pos + 8 + 24); }
+    else if (id == "data") { w.dpos = pos + 8; dlen = std::min(len, data.size() - w.dpos); }
     pos += 8 + len + (len & 1);
   }
-  if (!dpos || !channels || !bits) { if (err) *err = "WAV without fmt/data chunk: " + path; return false; }
-  if ((bits != 8 && bits != 16 && bits != 24 && bits != 32) || channels > 64) {
-    if (err) *err = "unsupported WAV format (" + std::to_string(bits) + " bits, " + std::to_string(channels) + " channels): " + path;
+  if (!w.dpos || !w.channels || !w.bits) { if (err) *err = "WAV without fmt/data chunk: " + path; return false; }
+  if ((w.bits != 8 && w.bits != 16 && w.bits != 24 && w.bits != 32) || w.channels > 64) {
+    if (err) *err = "unsupported WAV format (" + std::to_string(w.bits) + " bits, " + std::to_string(w.channels) + " channels): " + path;
     return false;
   }
-  const size_t bytes = bits / 8, frames = dlen / (bytes * channels);
-  out.resize(frames);
-  for (size_t f = 0; f < frames; ++f) {
-    double acc = 0.0;
-    for (uint32_t c = 0; c < channels; ++c) {
-      const size_t o = dpos + (f * channels + c) * bytes;
-      double v = 0.0;
-      if (fmt == 3 && bits == 32) { float x; std::memcpy(&x, &data[o], 4); v = x; }
-      else if (bits == 16) v = (int16_t)rd16(o) / 32768.0;                          // ints scaled by 2^(bits-1), A.10
-      else if (bits == 24) { int32_t x = (int32_t)(rd16(o) | ((uint32_t)(uint8_t)data[o + 2] << 16)); if (x & 0x800000) x |= ~0xFFFFFF; v = x / 8388608.0; }
-      else if (bits == 32) v = (int32_t)rd32(o) / 2147483648.0;
-      else if (bits == 8) v = ((uint8_t)data[o] - 128) / 128.0;
-      acc += v;
-    }
-    out[f] = (float)(acc / channels);
+  w.frames = dlen / ((size_t)(w.bits / 8) * w.channels);
+  return true;
+}
+} // namespace
+
+bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* sample_rate, std::string* err) {
+  WavData w;
+  if (!wav_open(path, w, err)) return false;
+  out.resize(w.frames);
+  for (size_t f = 0; f < w.frames; ++f) out[f] = w.mean(f);
+  if (sample_rate) *sample_rate = w.rate;
+  return true;
+}
+
+bool read_wav_stereo(const std::string& path, std::vector<float>& out, uint32_t* channels, uint32_t* sample_rate, std::string* err) {
+  WavData w;
+  if (!wav_open(path, w, err)) return false;
+  const uint32_t ch = w.channels == 2 ? 2u : 1u;
+  out.resize(w.frames * ch);
+  for (size_t f = 0; f < w.frames; ++f) {
+    if (ch == 2) { out[2 * f] = (float)w.value(f, 0); out[2 * f + 1] = (float)w.value(f, 1); }
+    else out[f] = w.mean(f);
   }
-  if (sample_rate) *sample_rate = rate;
+  if (channels) *channels = ch;
+  if (sample_rate) *sample_rate = w.rate;
   return true;
 }
 
@@ -582,12 +619,6 @@ void synthetic_707_kit(uint32_t sample_rate, std::vector<float>& pcm, std::vecto
     pcm.insert(pcm.end(), one.begin(), one.end());
   }
 }
-#ifndef GROOVE_HOST_PARSER_ONLY
-extern "C" int gh_add_drumkit(void*, const float*, uint64_t, const groove_sample_desc*, uint32_t, const int*);
-extern "C" int gh_add_welsh(void*, const groove_welsh_params*, uint32_t);
-extern "C" int gh_add_fm(void*, const groove_fm_params*, uint32_t);
-extern "C" int gh_add_sampler(void*, const float*, uint64_t, double, uint32_t);
-extern "C" int gh_add_toy_instrument(void*, double, double);
 // Where a sampler's file is looked for (the reference resolves it through groove_utils::Paths, absent from the tree): the assets'
 // samples directory, the assets directory, the project's own directory, the reference checkout's test-data (where the three
 // sampler projects' files lie: projects/tests/load-*-wav.json, projects/demos/instruments/sampler.json).
@@ -601,6 +632,14 @@ std::string find_sample_file(const std::string& name, const std::string& assets_
   for (const auto& t : tries) { std::ifstream f(t, std::ios::binary); if (f) return t; }
   return tries.empty() ? name : tries.front();
 }
+#ifndef GROOVE_HOST_PARSER_ONLY
+extern "C" int gh_add_drumkit(void*, const float*, uint64_t, const groove_sample_desc*, uint32_t, const int*);
+extern "C" int gh_add_drumkit_stereo(void*, const float*, uint64_t, const groove_sample_desc*, uint32_t, const int*);
+extern "C" int gh_add_sampler_stereo(void*, const float*, uint64_t, double, uint32_t);
+extern "C" int gh_add_welsh(void*, const groove_welsh_params*, uint32_t);
+extern "C" int gh_add_fm(void*, const groove_fm_params*, uint32_t);
+extern "C" int gh_add_sampler(void*, const float*, uint64_t, double, uint32_t);
+extern "C" int gh_add_toy_instrument(void*, double, double);
 #endif
 } // namespace
 
@@ -622,21 +661,37 @@ int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets
       std::vector<groove_sample_desc> descs;
       int key_to_sample[128];
       for (int& k : key_to_sample) k = -1;
+      bool stereo = false;
+      size_t kit_frames = 0;
       if (synthetic_kit) {
         synthetic_707_kit(o.sample_rate(), pcm, descs, key_to_sample);
       } else {
+        std::vector<std::vector<float>> files; // set_stereo_samples: a kit with a two-channel file is a stereo bank, its mono files on both channels
+        std::vector<uint32_t> file_ch;
         for (auto& km : k707) {
           std::vector<float> one;
           std::string err;
-          uint32_t sr = 0;
-          if (!read_wav_mono(assets_root + "/samples/elphnt.io/707/" + km.second, one, &sr, &err)) return o.fail(err);
-          groove_sample_desc sd{(uint64_t)pcm.size(), (uint32_t)one.size(), 0.0f};
-          key_to_sample[km.first] = (int)descs.size();
-          descs.push_back(sd);
-          pcm.insert(pcm.end(), one.begin(), one.end());
+          uint32_t sr = 0, ch = 1;
+          const std::string path = assets_root + "/samples/elphnt.io/707/" + km.second;
+          if (!(o.stereo_samples() ? read_wav_stereo(path, one, &ch, &sr, &err) : read_wav_mono(path, one, &sr, &err))) return o.fail(err);
+          stereo = stereo || ch == 2;
+          files.push_back(std::move(one)); file_ch.push_back(ch);
         }
+        size_t at = 0; // frames so far
+        for (size_t i = 0; i < files.size(); ++i) {
+          const std::vector<float>& one = files[i];
+          const size_t frames = one.size() / file_ch[i];
+          groove_sample_desc sd{(uint64_t)at, (uint32_t)frames, 0.0f};
+          key_to_sample[k707[i].first] = (int)descs.size();
+          descs.push_back(sd);
+          if (stereo && file_ch[i] == 1) for (float x : one) { pcm.push_back(x); pcm.push_back(x); }
+          else pcm.insert(pcm.end(), one.begin(), one.end());
+          at += frames;
+        }
+        kit_frames = at;
       }
-      uid = gh_add_drumkit(&o, pcm.data(), pcm.size(), descs.data(), (uint32_t)descs.size(), key_to_sample);
+      if (stereo) uid = gh_add_drumkit_stereo(&o, pcm.data(), kit_frames, descs.data(), (uint32_t)descs.size(), key_to_sample);
+      else uid = gh_add_drumkit(&o, pcm.data(), pcm.size(), descs.data(), (uint32_t)descs.size(), key_to_sample);
     } else if (d.kind == "welsh-raw") {
       uid = gh_add_welsh(&o, &d.welsh, 8);
     } else if (d.kind == "toy-instrument") {
@@ -647,12 +702,13 @@ int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets
       const std::string path = find_sample_file(d.name, assets_root, p.project_dir);
       std::vector<float> pcm;
       std::string err;
-      uint32_t sr = 0;
-      if (!read_wav_mono(path, pcm, &sr, &err)) return o.fail(err);
+      uint32_t sr = 0, ch = 1; // set_stereo_samples and a two-channel file: eight voices on a stereo bank
+      if (!(o.stereo_samples() ? read_wav_stereo(path, pcm, &ch, &sr, &err) : read_wav_mono(path, pcm, &sr, &err))) return o.fail(err);
       if (pcm.empty()) return o.fail("sampler: no frames in " + path);
       double root = d.root;
       if (!(root > 0.0)) { const int note = read_wav_root_note(path); root = note >= 0 ? note_to_frequency(note) : 440.0; }
-      uid = gh_add_sampler(&o, pcm.data(), pcm.size(), root, 8);
+      if (ch == 2) uid = gh_add_sampler_stereo(&o, pcm.data(), pcm.size() / 2, root, 8);
+      else uid = gh_add_sampler(&o, pcm.data(), pcm.size(), root, 8);
     } else {
       return o.fail("instrument kind '" + d.kind + "' is not an instrument kind (settings/src/instruments.rs:26-39)");
     }
@@ -726,10 +782,39 @@ int64_t gh_read_wav_mono(const char* path, float* out, uint64_t cap, uint32_t* s
   return (int64_t)v.size();
 }
 
+// read_wav_stereo for the tests: frames in the file, or -1 with a message; *channels is 1 or 2 and out receives
+// min(cap, frames * channels) floats (two channels: interleaved left, right).
+int64_t gh_read_wav_stereo(const char* path, float* out, uint64_t cap, uint32_t* channels, uint32_t* sample_rate, char* err, size_t err_cap) {
+  std::vector<float> v;
+  std::string e;
+  uint32_t ch = 1;
+  if (!groove_host::read_wav_stereo(path, v, &ch, sample_rate, &e)) {
+    if (err && err_cap) { std::snprintf(err, err_cap, "%s", e.c_str()); }
+    return -1;
+  }
+  if (channels) *channels = ch;
+  const uint64_t n = std::min<uint64_t>(cap, v.size());
+  if (n && out) std::memcpy(out, v.data(), n * sizeof(float));
+  return (int64_t)(v.size() / ch);
+}
+
 // Parse only (no GPU): returns a malloc'ed JSON summary, or NULL and the message in err[0..err_len).
 char* gh_project_describe(const char* path, const char* assets_root, char* err, size_t err_len) {
   try {
     const std::string s = describe(parse_project_file(path, assets_root ? assets_root : ""));
+    char* out = (char*)std::malloc(s.size() + 1);
+    std::memcpy(out, s.c_str(), s.size() + 1);
+    return out;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+// gh_project_describe with the sampler devices' "channels" as Orchestrator::set_stereo_samples(stereo_samples) would make their banks
+char* gh_project_describe_samples(const char* path, const char* assets_root, int stereo_samples, char* err, size_t err_len) {
+  try {
+    const std::string root = assets_root ? assets_root : "";
+    const std::string s = describe(parse_project_file(path, root), root, stereo_samples != 0);
     char* out = (char*)std::malloc(s.size() + 1);
     std::memcpy(out, s.c_str(), s.size() + 1);
     return out;

@@ -76,7 +76,9 @@ std::string patch_name_to_settings_name(const std::string& name);
 ProjectDesc parse_project(const std::string& json_text, const std::string& assets_root);
 ProjectDesc parse_project_file(const std::string& path, const std::string& assets_root);
 // A compact JSON rendering of a ProjectDesc (used by the tests).
-std::string describe(const ProjectDesc& p);
+// A `sampler` device carries "channels": those of the bank instantiate() would make of its file with
+// Orchestrator::set_stereo_samples(stereo_samples) — 1 with the switch off, whatever the file holds.
+std::string describe(const ProjectDesc& p, const std::string& assets_root = "", bool stereo_samples = false);
 
 // WelshSynthParams as the project file carries it for `welsh-raw` (settings/src/instruments.rs:30-31; the struct settings/src/patches.rs:110-169
 // builds): {"voice": {"oscillator-1": {"waveform", "frequency-tune"}, .., "amp-envelope", "lfo", "lfo-routing", "lfo-depth", "filter":
@@ -87,12 +89,18 @@ groove_welsh_params welsh_params_from_raw_json(const json5::Value& params, std::
 int read_wav_root_note(const std::string& path);
 // Mono PCM from a WAV file (16/24/32-bit int or 32-bit float, any channel count: channels averaged).
 bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* sample_rate, std::string* err);
+// The same parser, keeping the channels of a two-channel file: *channels = 2 and `out` holds interleaved left, right, each the (float) of
+// the decoded value.  A one-channel file gives *channels = 1 and its values; a file of MORE than two channels also gives *channels = 1 and
+// read_wav_mono's mean of all channels (nothing in the reference says what such a file should sound like; no shipped asset is one).
+bool read_wav_stereo(const std::string& path, std::vector<float>& out, uint32_t* channels, uint32_t* sample_rate, std::string* err);
 
 // The instantiate() half: devices → entities, patch cables, MIDI routing, tracks → Sequencer,
 // trips → ControlTrip.  With `synthetic_kit` the drumkit uses a generated sample bank instead of
 // <assets>/samples/elphnt.io/707 (the GPU box has no reference assets).
 // With Orchestrator::set_filter_links_on_device(true) / set_wet_links_on_device(true) set beforehand, the project's held_controls onto
 // filter parameters / wet-dry-mix are linked too.
+// With Orchestrator::set_stereo_samples(true) a `sampler` on a two-channel file is eight voices on a stereo bank, and a `drumkit` any of
+// whose files has two channels is a stereo bank with its mono files on both channels (--synthetic-kit stays mono).
 int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets_root, bool synthetic_kit);
 
 } // namespace groove_host

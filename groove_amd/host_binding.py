@@ -24,6 +24,9 @@ def load():
         "gh_last_error": (C.c_char_p, [vp]), "gh_add_toy_source": (i, [vp, d]),
         "gh_add_welsh": (i, [vp, C.POINTER(T.WelshParams), u32]), "gh_add_fm": (i, [vp, C.POINTER(T.FmParams), u32]),
         "gh_add_drumkit": (i, [vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), u32, C.POINTER(C.c_int)]),
+        "gh_add_drumkit_stereo": (i, [vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), u32, C.POINTER(C.c_int)]),
+        "gh_add_sampler": (i, [vp, _fp, C.c_uint64, d, u32]), "gh_add_sampler_stereo": (i, [vp, _fp, C.c_uint64, d, u32]),
+        "gh_set_stereo_samples": (None, [vp, i]), "gh_stereo_samples": (i, [vp]),
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
@@ -80,6 +83,26 @@ class Orchestrator:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         k2s = (C.c_int * 128)(*key_to_sample)
         return self.L.gh_add_drumkit(self.h, pcm.ctypes.data_as(_fp), pcm.size, descs, len(descs), k2s)
+
+    def add_drumkit_stereo(self, pcm_lr, descs, key_to_sample):
+        """A drumkit over a stereo bank: pcm_lr is [frames, 2] (left, right per frame), descs in frames."""
+        pcm = np.ascontiguousarray(pcm_lr, dtype=np.float32)
+        assert pcm.ndim == 2 and pcm.shape[1] == 2, pcm.shape
+        k2s = (C.c_int * 128)(*key_to_sample)
+        return self.L.gh_add_drumkit_stereo(self.h, pcm.ctypes.data_as(_fp), pcm.shape[0], descs, len(descs), k2s)
+
+    def add_sampler(self, pcm, root_hz, voices=8):
+        """A sampler on one buffer: [frames] mono, or [frames, 2] stereo (gh_add_sampler_stereo)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        add = self.L.gh_add_sampler_stereo if pcm.ndim == 2 else self.L.gh_add_sampler
+        return add(self.h, pcm.ctypes.data_as(_fp), pcm.shape[0], root_hz, voices)
+
+    def set_stereo_samples(self, on):
+        """Projects instantiated from here on keep the channels of two-channel sample files: a sampler on one is a stereo bank, a drumkit
+        with one is a stereo bank whose mono files are on both channels.  Off by default (a stereo file is the mean of its channels)."""
+        self.L.gh_set_stereo_samples(self.h, 1 if on else 0)
+
+    def stereo_samples(self): return bool(self.L.gh_stereo_samples(self.h))
 
     def add_effect(self, kind, params): return self.L.gh_add_effect(self.h, kind, C.byref(params))
     def patch(self, source, sink): return self.L.gh_patch(self.h, source, sink)

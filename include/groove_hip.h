@@ -173,6 +173,18 @@ int groove_fm_create(groove_ctx* ctx, const groove_fm_params* p, uint32_t n, gro
 int groove_sampler_create(groove_ctx* ctx, const float* bank_pcm, uint64_t bank_frames,
                           const groove_sample_desc* descs, uint32_t n_samples,
                           const groove_sampler_params* p, uint32_t n, groove_bank** out);
+/* The same bank over STEREO sample memory: bank_pcm_lr is [bank_frames][2] fp32, interleaved left, right; groove_sample_desc is
+ * unchanged (offset and length in frames).  A voice steps and ends exactly as a mono bank's does (same parameter and state records,
+ * same groove_bank_state_words / _download_state), and its output is L = left[offset + i] * gain, R = right[offset + i] * gain.
+ * Stereo is a property of the bank: a kit that mixes mono and stereo files is a stereo bank whose mono files the caller writes into
+ * both channels.  Everything that takes a sampler bank takes this one (note events, reset, groove_bank_set_param and links onto
+ * GROOVE_CTL_SAMPLER_GAIN, the four render entries, groove_bank_kernel_form: same strings and thresholds).  Same argument checks as
+ * groove_sampler_create, reported under this function's name. */
+int groove_sampler_create_stereo(groove_ctx* ctx, const float* bank_pcm_lr, uint64_t bank_frames,
+                                 const groove_sample_desc* descs, uint32_t n_samples,
+                                 const groove_sampler_params* p, uint32_t n, groove_bank** out);
+/* Channels of a sampler bank's sample memory: 1 (groove_sampler_create) or 2 (groove_sampler_create_stereo); 0 for any other bank. */
+uint32_t groove_bank_sample_channels(groove_bank* bank);
 int groove_bank_destroy(groove_bank* bank);
 uint32_t groove_bank_voices(groove_bank* bank);
 /* HandlesMidi::handle_midi_message → PlaysNotes::note_on/note_off (orchestrator.rs:737-739;
@@ -249,7 +261,8 @@ int groove_bank_render_mix_deferred(groove_bank* bank, uint32_t frames, float* b
  * deferred exactly as above (carried by the next such call, or flushed).  For projects with at most one time-parallel bank of each
  * kind and at most 2,048 partial rows in all (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096 sampler
  * voices, three launches whose durations added -> one); anything else is rendered bank by bank by groove_bank_render_mix_deferred in
- * the order given (bus = banks[0] (+)= ... ).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
+ * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them always takes that bank-by-bank path (the one
+ * launch's sampler body is the mono one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
  * the same bits (one reduction over all rows instead of one per bank).  No reference counterpart as a call: the reference ticks
  * every instrument inside gather_audio. */
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate);
