@@ -24,6 +24,8 @@ CTL_FX_CEILING, CTL_FX_BITS, CTL_FX_CUTOFF, CTL_FX_Q, CTL_FX_PASSBAND_RIPPLE, CT
 CTL_WELSH_DCA_GAIN, CTL_WELSH_DCA_PAN, CTL_WELSH_CUTOFF = 32, 33, 34
 CTL_FM_DCA_GAIN, CTL_FM_DCA_PAN, CTL_FM_DEPTH, CTL_FM_BETA = 48, 49, 50, 51     # FM banks (`ratio` has no control)
 CTL_SAMPLER_GAIN = 64                                                            # sampler and drumkit banks
+# groove_sample_interpolation
+SAMPLE_NEAREST, SAMPLE_LINEAR, SAMPLE_CUBIC = range(3)
 # groove_ctl_source_kind, groove_ctl_law
 CTL_SRC_LFO, CTL_SRC_SIGNAL, CTL_SRC_TRIP = range(3)
 # groove_ctl_step_kind, GROOVE_CTL_UNITS_PER_BEAT

@@ -1426,6 +1426,134 @@ GROOVE_HD void sampler_chunk_stereo(const SamplerParams& p, SamplerState& s, con
   if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
 }
 
+// INTERPOLATED playback (groove_bank_set_sample_interpolation; docs/DSP_SPEC.md section 7): a bank property that changes the value a
+// frame plays and nothing else — cursor, end rule, notes and the state record are the ones above, in every mode.  A frame at cursor
+// pos reads the taps i + FIRST .. i + FIRST + N - 1 around i = pos >> 44 and weighs them by t, the top 24 bits of pos's fraction.
+template <int MODE> struct SampleTaps {
+  static_assert(MODE == GROOVE_SAMPLE_NEAREST || MODE == GROOVE_SAMPLE_LINEAR || MODE == GROOVE_SAMPLE_CUBIC, "unknown interpolation mode");
+  static constexpr int N = MODE == GROOVE_SAMPLE_CUBIC ? 4 : MODE == GROOVE_SAMPLE_LINEAR ? 2 : 1; // taps per frame
+  static constexpr int FIRST = MODE == GROOVE_SAMPLE_CUBIC ? -1 : 0;                                // the first tap, relative to i
+};
+GROOVE_HD float sample_fraction(uint64_t pos) { return (float)(uint32_t)((pos >> 20) & 0xFFFFFFu) * 5.9604644775390625e-8f; } // 24 bits * 2^-24: exact, in [0, 1)
+// Tap i + k of a sample of `length` frames: a tap before the first or past the last frame is 0.0f (the sample begins from and ends
+// into silence) and is NEVER fetched from its own address — the shared bank holds other samples on both sides — but from the nearest
+// frame inside the sample, and then dropped by the select.
+GROOVE_HD bool sample_tap_inside(uint32_t i, int k, uint32_t length) { const int32_t j = (int32_t)i + k; return j >= 0 && (uint32_t)j < length; } // (i < 2^20)
+GROOVE_HD uint32_t sample_tap_clamped(uint32_t i, int k, uint32_t length) { const int32_t j = (int32_t)i + k; return j < 0 ? 0u : ((uint32_t)j < length ? (uint32_t)j : length - 1); }
+// q: the N taps from FIRST on.  Explicit fmaf throughout, so that every compilation of this text rounds alike.  Both formulas give
+// q[-FIRST] exactly at t == 0: an integer step plays NEAREST's bits.
+template <int MODE>
+GROOVE_HD float sample_interp(const float (&q)[SampleTaps<MODE>::N], float t) {
+  if constexpr (MODE == GROOVE_SAMPLE_LINEAR) {
+    return fmaf(t, q[1] - q[0], q[0]);
+  } else if constexpr (MODE == GROOVE_SAMPLE_CUBIC) { // Catmull-Rom through q[1] (t = 0) and q[2] (t = 1), Horner form
+    const float c0 = q[1];
+    const float c1 = 0.5f * (q[2] - q[0]);
+    const float c2 = fmaf(-0.5f, q[3], fmaf(2.0f, q[2], fmaf(-2.5f, q[1], q[0])));
+    const float c3 = fmaf(1.5f, q[1] - q[2], 0.5f * (q[3] - q[0]));
+    return fmaf(fmaf(fmaf(c3, t, c2), t, c1), t, c0);
+  } else {
+    return q[0];
+  }
+}
+// The per-frame DEFINITION, mono and stereo (MODE NEAREST: sampler_frame / sampler_frame_stereo, bit for bit).
+template <int MODE>
+GROOVE_HD float sampler_frame_interp(const SamplerParams& p, SamplerState& s, const float* bank) {
+  using T = SampleTaps<MODE>;
+  if (!s.playing) return 0.0f;
+  const uint32_t i = (uint32_t)(s.idx >> 44);
+  if (i >= p.length) { s.playing = 0; return 0.0f; }
+  float q[T::N];
+  for (int m = 0; m < T::N; ++m) {
+    const float x = bank[(size_t)p.offset + sample_tap_clamped(i, T::FIRST + m, p.length)];
+    q[m] = sample_tap_inside(i, T::FIRST + m, p.length) ? x : 0.0f;
+  }
+  const float v = sample_interp<MODE>(q, sample_fraction(s.idx)) * p.gain;
+  s.idx += s.step;
+  return v;
+}
+template <int MODE>
+GROOVE_HD void sampler_frame_interp_stereo(const SamplerParams& p, SamplerState& s, const SamplePair* bank, float& L, float& R) {
+  using T = SampleTaps<MODE>;
+  L = R = 0.0f;
+  if (!s.playing) return;
+  const uint32_t i = (uint32_t)(s.idx >> 44);
+  if (i >= p.length) { s.playing = 0; return; }
+  float ql[T::N], qr[T::N];
+  for (int m = 0; m < T::N; ++m) {
+    const SamplePair x = bank[(size_t)p.offset + sample_tap_clamped(i, T::FIRST + m, p.length)];
+    const bool in = sample_tap_inside(i, T::FIRST + m, p.length);
+    ql[m] = in ? x.l : 0.0f;
+    qr[m] = in ? x.r : 0.0f;
+  }
+  const float t = sample_fraction(s.idx);
+  L = sample_interp<MODE>(ql, t) * p.gain;
+  R = sample_interp<MODE>(qr, t) * p.gain;
+  s.idx += s.step;
+}
+// sampler_chunk / sampler_chunk_stereo for an interpolated bank: all C * N fetches issued from clamped addresses before any is used.
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_interp(const SamplerParams& p, SamplerState& s, const float* bank, uint32_t count, float (&v)[C]) {
+  using T = SampleTaps<MODE>;
+  uint32_t valid = 0; // frames of the chunk that play
+  float raw[C][T::N];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint32_t i = (uint32_t)((s.idx + (uint64_t)k * s.step) >> 44);
+    const bool ok = s.playing && (uint32_t)k < count && i < p.length;
+    const uint32_t ic = i < p.length ? i : p.length - 1;
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) raw[k][m] = bank[(size_t)p.offset + sample_tap_clamped(ic, T::FIRST + m, p.length)];
+    valid += ok ? 1u : 0u;
+    v[k] = ok ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint64_t pos = s.idx + (uint64_t)k * s.step;
+    const uint32_t i = (uint32_t)(pos >> 44);
+    float q[T::N];
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) q[m] = sample_tap_inside(i, T::FIRST + m, p.length) ? raw[k][m] : 0.0f;
+    v[k] = v[k] != 0.0f ? sample_interp<MODE>(q, sample_fraction(pos)) * p.gain : 0.0f;
+  }
+  s.idx += (uint64_t)valid * s.step;
+  if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+}
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_interp_stereo(const SamplerParams& p, SamplerState& s, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) {
+  using T = SampleTaps<MODE>;
+  uint32_t valid = 0; // frames of the chunk that play
+  SamplePair raw[C][T::N];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint32_t i = (uint32_t)((s.idx + (uint64_t)k * s.step) >> 44);
+    const bool ok = s.playing && (uint32_t)k < count && i < p.length;
+    const uint32_t ic = i < p.length ? i : p.length - 1;
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) raw[k][m] = bank[(size_t)p.offset + sample_tap_clamped(ic, T::FIRST + m, p.length)];
+    valid += ok ? 1u : 0u;
+    l[k] = ok ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint64_t pos = s.idx + (uint64_t)k * s.step;
+    const uint32_t i = (uint32_t)(pos >> 44);
+    const bool ok = l[k] != 0.0f;
+    float ql[T::N], qr[T::N];
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) {
+      const bool in = sample_tap_inside(i, T::FIRST + m, p.length);
+      ql[m] = in ? raw[k][m].l : 0.0f;
+      qr[m] = in ? raw[k][m].r : 0.0f;
+    }
+    const float t = sample_fraction(pos);
+    l[k] = ok ? sample_interp<MODE>(ql, t) * p.gain : 0.0f;
+    r[k] = ok ? sample_interp<MODE>(qr, t) * p.gain : 0.0f;
+  }
+  s.idx += (uint64_t)valid * s.step;
+  if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+}
+
 // ------------------------------------------------------------------ effects (a8, a9)
 GROOVE_HD float bitcrush(float x, uint32_t bits) {
   float ax = fabsf(x) * 32767.0f;

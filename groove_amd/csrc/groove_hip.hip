@@ -127,6 +127,7 @@ struct groove_bank {
   size_t wg_list_cap = 0;
   float* d_pcm = nullptr;   // sampler bank: [bank_frames] values, or [bank_frames] interleaved left, right pairs ...
   bool pcm_stereo = false;  // ... of a stereo bank (groove_sampler_create_stereo): picks the kernels' STEREO instantiations
+  uint32_t pcm_interp = GROOVE_SAMPLE_NEAREST; // sampler bank: a groove_sample_interpolation, read at every launch (picks the kernels' MODE instantiations)
   // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
   // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
   // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one).  fm: the same owner with CTL_FM_WORDS rows — gain, pan, depth,
@@ -1564,6 +1565,19 @@ int groove_sampler_create_stereo(groove_ctx* ctx, const float* bank_pcm_lr, uint
   return sampler_create("groove_sampler_create_stereo", 2, ctx, bank_pcm_lr, bank_frames, descs, n_samples, p, n, out);
 }
 uint32_t groove_bank_sample_channels(groove_bank* b) { return b && b->kind == BANK_SAMPLER ? (b->pcm_stereo ? 2u : 1u) : 0u; }
+// A host-side switch between kernel instantiations: neither parameters nor state are touched.  Joined first like groove_bank_set_param,
+// so that the order of effects is the order of calls whatever streams the bank's earlier blocks run on.
+int groove_bank_set_sample_interpolation(groove_bank* b, uint32_t mode) {
+  if (!b) return fail(nullptr, "groove_bank_set_sample_interpolation: bank is NULL");
+  groove_ctx* ctx = b->ctx;
+  if (b->kind != BANK_SAMPLER) return fail(ctx, "groove_bank_set_sample_interpolation: only sampler and drumkit banks play samples");
+  if (mode != GROOVE_SAMPLE_NEAREST && mode != GROOVE_SAMPLE_LINEAR && mode != GROOVE_SAMPLE_CUBIC)
+    return fail(ctx, "groove_bank_set_sample_interpolation: unknown mode (0 nearest, 1 linear, 2 cubic)");
+  if (ctx_join(ctx)) return 1;
+  b->pcm_interp = mode;
+  return 0;
+}
+uint32_t groove_bank_sample_interpolation(groove_bank* b) { return b && b->kind == BANK_SAMPLER ? b->pcm_interp : (uint32_t)GROOVE_SAMPLE_NEAREST; }
 int groove_bank_destroy(groove_bank* b) {
   if (!b) return 0;
   groove_ctx* ctx = b->ctx;
@@ -1774,6 +1788,15 @@ static void launch_small_uniform(const groove_bank* b, const UniformArgs& a, hip
     launch_welsh_kind(k, r, st, fused, (k == 5 || !p.count[5]) ? done : nullptr);
   }
 }
+// The serial sampler kernel of an interpolated bank (MODE LINEAR or CUBIC).
+extern "C++" template <int MODE>
+static void launch_sampler_serial_interp(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
+  if (b->pcm_stereo) {
+    if (fused) launch_bound(sampler_render_kernel<true, true, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+    else launch_bound(sampler_render_kernel<false, true, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+  } else if (fused) launch_bound(sampler_render_kernel<true, false, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+  else launch_bound(sampler_render_kernel<false, false, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+}
 // Every form but the big uniform one is ONE launch sequence on ONE stream, and this is where it is launched.  fused: `rows` =
 // partial rows only; otherwise `out` = the planar block and `rows` = its row sums (kernels.h run_frames), null for none.
 // `done` (optional) completes with the (last) kernel: bound to the dispatch (kernels.h launch_bound).  `prev`: the previous
@@ -1789,7 +1812,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (prev) a.prev = *prev;
       if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
       if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
-      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
+      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->pcm_interp, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
       else { a.full_coef = b->plan.tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
       break;
     }
@@ -1808,7 +1831,9 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       else launch_bound(fm_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows);
       break;
     case Form::SamplerSerial:
-      if (b->pcm_stereo) {
+      if (b->pcm_interp == GROOVE_SAMPLE_LINEAR) launch_sampler_serial_interp<GROOVE_SAMPLE_LINEAR>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+      else if (b->pcm_interp == GROOVE_SAMPLE_CUBIC) launch_sampler_serial_interp<GROOVE_SAMPLE_CUBIC>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+      else if (b->pcm_stereo) {
         if (fused) launch_bound(sampler_render_kernel<true, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
         else launch_bound(sampler_render_kernel<false, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
       } else if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
@@ -2190,7 +2215,7 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
 // groove_bank_render_mix_deferred for SEVERAL small banks of different kinds at once: ONE launch for the whole block (welsh_tp.h
 // tp_mixed_kernel: a grid whose workgroups dispatch on their index into the Welsh / FM / sampler time-parallel bodies), one row
 // buffer, one carried reduction — Orchestrator::gather_audio's one sum over all instruments (orchestrator.rs:397-410).  Takes
-// projects with at most one time-parallel bank of each kind, no stereo sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
+// projects with at most one time-parallel bank of each kind, no stereo or interpolated sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
 // through groove_bank_render_mix_deferred, in the order given.
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate) {
   if (!ctx || !bus_dev || (n_banks && !banks)) return fail(ctx, "groove_banks_render_mix_deferred: NULL argument");
@@ -2207,7 +2232,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
     if (!b) return fail(ctx, "groove_banks_render_mix_deferred: NULL bank");
     if (b->ctx != ctx) return fail(ctx, "groove_banks_render_mix_deferred: a bank of another ctx");
     const int k = b->kind == BANK_WELSH ? 0 : b->kind == BANK_FM ? 1 : 2;
-    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo) ok = false; // (tp_mixed_kernel's sampler body is the mono one)
+    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo || b->pcm_interp != GROOVE_SAMPLE_NEAREST) ok = false; // (tp_mixed_kernel's sampler body is the mono, nearest one)
     of_kind[k] = b;
   }
   TpMixedArgs m{};
@@ -2294,9 +2319,12 @@ const char* groove_bank_kernel_form(groove_bank* b, uint32_t frames, int fused) 
     case Form::TimeParallel:
       if (b->kind == BANK_WELSH) return tp_vpw(b) == 2 ? "welsh_tp_kernel (time-parallel, two voices per wavefront)" : "welsh_tp_kernel (time-parallel, one wavefront per voice)";
       if (b->kind == BANK_FM) return tp_vpw(b) == 4 ? "fm_tp_kernel (time-parallel, four voices per wavefront)" : "fm_tp_kernel (time-parallel)";
-      return "sampler_tp_kernel (time-parallel)";
+      return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_tp_kernel (time-parallel, linear interpolation)"
+           : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_tp_kernel (time-parallel, cubic interpolation)" : "sampler_tp_kernel (time-parallel)";
     case Form::FmSerial: return "fm_render_kernel (serial, one voice per lane)";
-    case Form::SamplerSerial: return "sampler_render_kernel (serial, one voice per lane)";
+    case Form::SamplerSerial:
+      return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_render_kernel (serial, one voice per lane, linear interpolation)"
+           : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_render_kernel (serial, one voice per lane, cubic interpolation)" : "sampler_render_kernel (serial, one voice per lane)";
     case Form::WelshPerLane: return "welsh_render_kernel (per-lane parameters)";
     case Form::WelshBigUniform: // fused: groove_bank_render_mix takes render_mix_pipelined; otherwise groove_bank_render's walk (launch_render)
       return fused ? "welsh_render_uniform_mix_kernel (big-bank form: three launches per block over thirds of the kind-sorted workgroups, one launch per base kind for the exact-f64 kinds only; class-specialised bodies, blocks pipelined)"

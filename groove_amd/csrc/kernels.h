@@ -872,7 +872,10 @@ __global__ __launch_bounds__(kThreads) void fm_render_kernel(
 
 // a7 SamplerVoice: pointer stepping; the shared bank is a gather served from L2 / MALL.  STEREO: `bank` holds interleaved left, right
 // frames (dsp_core.h SamplePair; one 8-byte fetch per frame), and the two channels are two values all the way to the bus.
-template <bool FUSED, bool STEREO = false>
+// MODE (groove_sample_interpolation): LINEAR and CUBIC read 2 and 4 taps per frame (dsp_core.h sampler_chunk_interp: 16 * N fetches in
+// flight); the NEAREST instantiations are the text they were.  CUBIC STEREO holds 16 * 4 * 2 = 128 fetched values: 220 VGPRs of
+// the 512 a 256-thread workgroup may use, no scratch (the compiler's resource table), so the chunk stays 16 frames in every instantiation.
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
 __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n, uint32_t frames,
     size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank) {
@@ -889,7 +892,10 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t count = min(C, frames - f0);
     float x[C];
     float xr[STEREO ? C : 1]; // (a stereo bank's right channel; a mono voice is duplicated to both channels)
-    if constexpr (STEREO) sampler_chunk_stereo<C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
+    if constexpr (MODE != GROOVE_SAMPLE_NEAREST) {
+      if constexpr (STEREO) sampler_chunk_interp_stereo<MODE, C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
+      else sampler_chunk_interp<MODE, C>(p, s, bank, count, x);
+    } else if constexpr (STEREO) sampler_chunk_stereo<C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
     else sampler_chunk<C>(p, s, bank, count, x);
 #pragma unroll
     for (uint32_t k = 0; k < C; ++k) {

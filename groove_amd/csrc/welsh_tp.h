@@ -873,7 +873,9 @@ template <int WAVES> struct SamplerTpSmem<WAVES, true> { // a stereo bank: the l
 // WAVES wavefronts per workgroup: 16 in the bank's own kernel, 4 in the mixed kernel (whose workgroups are 256 threads)
 // STEREO: `bank` holds interleaved left, right frames (dsp_core.h SamplePair): one 8-byte fetch per frame, two accumulators per frame,
 // two tiles; each channel's sum is taken in the order the mono sum is (voice order within a wave, wave order within the workgroup).
-template <bool FUSED, int WAVES, bool STEREO = false>
+// MODE (groove_sample_interpolation): LINEAR and CUBIC fetch a frame's 2 or 4 taps (dsp_core.h SampleTaps, sample_interp) where NEAREST
+// fetches one value; `valid`, ok[][] and the state are the same in every mode, and the NEAREST instantiations are the text they were.
+template <bool FUSED, int WAVES, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
 __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES, STEREO>& sm) {
   float (&s_tile)[WAVES][kTpMaxFrames] = sm.tile;
   volatile uint32_t (&s_ev)[WAVES][64] = sm.ev;
@@ -918,7 +920,14 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
 #pragma unroll
   for (uint32_t j = 0; j < kTpChunk; ++j) { acc[j] = 0.0f; if constexpr (STEREO) acc_r[j] = 0.0f; }
   const uint32_t idx_lo = (uint32_t)s0.idx, idx_hi = (uint32_t)(s0.idx >> 32), step_lo = (uint32_t)s0.step, step_hi = (uint32_t)(s0.step >> 32);
-  constexpr uint32_t U = 4; // voices whose fetches are issued together
+  using Taps = SampleTaps<MODE>;
+  constexpr bool INTERP = MODE != GROOVE_SAMPLE_NEAREST;
+  // voices whose fetches are issued together: 4.  An interpolated bank holds U x 4 frames x N taps x 1 or 2 channels of fetched values,
+  // and a 1,024-thread workgroup has 128 VGPRs per lane: with 4 voices LINEAR stereo (64 values), CUBIC mono (64) and CUBIC stereo (128)
+  // spill to scratch (the compiler's resource table: 116 - 188 bytes per lane), so those chunks are shortened to the 32 values LINEAR
+  // mono has in flight — 2, 2 and 1 voices.
+  constexpr uint32_t U = INTERP ? 8u / (uint32_t)(Taps::N * (STEREO ? 2 : 1)) : 4u;
+  static_assert(U >= 1 && U <= 4, "voices per fetch group");
   for (uint32_t k0 = 0; k0 < cnt; k0 += U) { // k is wave-uniform: v_readlane
     uint32_t off[U], len[U], playing[U];
     float gain[U];
@@ -938,6 +947,8 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     if (!any) continue; // (uniform)
     float raw[U][kTpChunk];
     float raw_r[STEREO ? U : 1][STEREO ? kTpChunk : 1];
+    float tap[INTERP ? U : 1][INTERP ? kTpChunk : 1][Taps::N];                      // an interpolated bank's taps (left ones of a stereo bank) ...
+    float tap_r[INTERP && STEREO ? U : 1][INTERP && STEREO ? kTpChunk : 1][Taps::N]; // ... and the right ones
     bool ok[U][kTpChunk];
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
@@ -946,7 +957,19 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
         const uint32_t f = n0 + j;
         const uint32_t i = (uint32_t)((idx[u] + (uint64_t)f * step[u]) >> 44);
         ok[u][j] = playing[u] && f < frames && i < len[u];
-        if constexpr (STEREO) {
+        if constexpr (INTERP) {
+          const uint32_t ic = i < len[u] ? i : len[u] - 1;
+#pragma unroll
+          for (int m = 0; m < Taps::N; ++m) {
+            const size_t at = (size_t)off[u] + sample_tap_clamped(ic, Taps::FIRST + m, len[u]);
+            if constexpr (STEREO) {
+              const SamplePair t = reinterpret_cast<const SamplePair*>(bank)[at];
+              tap[u][j][m] = t.l; tap_r[u][j][m] = t.r;
+            } else {
+              tap[u][j][m] = bank[at];
+            }
+          }
+        } else if constexpr (STEREO) {
           const SamplePair t = reinterpret_cast<const SamplePair*>(bank)[(size_t)off[u] + (i < len[u] ? i : len[u] - 1)];
           raw[u][j] = t.l; raw_r[u][j] = t.r;
         } else {
@@ -961,6 +984,20 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
       float x_r[STEREO ? kTpChunk : 1];
 #pragma unroll
       for (uint32_t j = 0; j < kTpChunk; ++j) {
+        if constexpr (INTERP) { // the taps past either end of the sample dropped, then the mode's formula at this frame's fraction
+          const uint64_t pos = idx[u] + (uint64_t)(n0 + j) * step[u];
+          const uint32_t i = (uint32_t)(pos >> 44);
+          const float t = sample_fraction(pos);
+          float q[Taps::N];
+#pragma unroll
+          for (int m = 0; m < Taps::N; ++m) q[m] = sample_tap_inside(i, Taps::FIRST + m, len[u]) ? tap[u][j][m] : 0.0f;
+          raw[u][j] = sample_interp<MODE>(q, t);
+          if constexpr (STEREO) {
+#pragma unroll
+            for (int m = 0; m < Taps::N; ++m) q[m] = sample_tap_inside(i, Taps::FIRST + m, len[u]) ? tap_r[u][j][m] : 0.0f;
+            raw_r[u][j] = sample_interp<MODE>(q, t);
+          }
+        }
         x[j] = ok[u][j] ? raw[u][j] * gain[u] : 0.0f; acc[j] += x[j];
         if constexpr (STEREO) { x_r[j] = ok[u][j] ? raw_r[u][j] * gain[u] : 0.0f; acc_r[j] += x_r[j]; }
       }
@@ -1010,10 +1047,10 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     soa_store(a.state, n, v, s);
   }
 }
-template <bool FUSED, bool STEREO = false>
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
 __global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw) {
   __shared__ SamplerTpSmem<kSamplerTpWaves, STEREO> sm;
-  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO>(a, bank, ie, vpw, tp_wg_own(), sm);
+  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO, MODE>(a, bank, ie, vpw, tp_wg_own(), sm);
 }
 // ------------------------------------------------------------------ several small banks in ONE launch (round 5)
 // A project of a few small banks of different kinds (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096
@@ -1059,7 +1096,7 @@ inline uint32_t mixed_sampler_workgroups(uint32_t n, uint32_t vpw) { const uint3
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done = nullptr); // welsh.vpw 1 | 2, fm.vpw 1 | 4
 void launch_welsh_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.bq_coef set (block-writing form): the BiQuad head fused; done: an event bound to the dispatch
 void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.vpw voices per wavefront (1, 2, 4)
-void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames; interpolation: a groove_sample_interpolation
 inline uint32_t welsh_tp_workgroups(uint32_t n, uint32_t vpw = 1) { return (n + kTpWaves * vpw - 1) / (kTpWaves * vpw); } // FM: groups of 4 vpw voices per workgroup, plain order
 inline uint32_t welsh_tp_grid(uint32_t n, uint32_t vpw = 1) { // Welsh: padded for the XCD-aware mapping (idle workgroups write zero rows)
   const uint32_t g = welsh_tp_workgroups(n, vpw);

@@ -42,10 +42,20 @@ void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done) 
   else if (a.vpw == 2) launch_fm_tp_vpw<2>(a, st, fused, done);
   else launch_fm_tp_vpw<1>(a, st, fused, done);
 }
-void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
+template <int MODE> // an interpolated bank (LINEAR, CUBIC)
+static void launch_sampler_tp_interp(const TpArgs& a, const float* bank, bool stereo, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done, dim3 grid, dim3 blk, uint32_t vpw) {
+  if (stereo) {
+    if (fused) launch_bound(sampler_tp_kernel<true, true, MODE>, grid, blk, st, done, a, bank, ie, vpw);
+    else launch_bound(sampler_tp_kernel<false, true, MODE>, grid, blk, st, done, a, bank, ie, vpw);
+  } else if (fused) launch_bound(sampler_tp_kernel<true, false, MODE>, grid, blk, st, done, a, bank, ie, vpw);
+  else launch_bound(sampler_tp_kernel<false, false, MODE>, grid, blk, st, done, a, bank, ie, vpw);
+}
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
   const uint32_t vpw = a.vpw > 1 ? a.vpw : sampler_tp_vpw(a.n); // (a.vpw: the deferred form's choice)
   const dim3 grid(sampler_tp_workgroups(a.n, vpw)), blk(kSamplerTpThreads);
-  if (stereo) {
+  if (interpolation == GROOVE_SAMPLE_LINEAR) launch_sampler_tp_interp<GROOVE_SAMPLE_LINEAR>(a, bank, stereo, ie, st, fused, done, grid, blk, vpw);
+  else if (interpolation == GROOVE_SAMPLE_CUBIC) launch_sampler_tp_interp<GROOVE_SAMPLE_CUBIC>(a, bank, stereo, ie, st, fused, done, grid, blk, vpw);
+  else if (stereo) {
     if (fused) launch_bound(sampler_tp_kernel<true, true>, grid, blk, st, done, a, bank, ie, vpw);
     else launch_bound(sampler_tp_kernel<false, true>, grid, blk, st, done, a, bank, ie, vpw);
   } else if (fused) launch_bound(sampler_tp_kernel<true>, grid, blk, st, done, a, bank, ie, vpw);

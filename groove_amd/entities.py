@@ -410,6 +410,16 @@ class Sampler(Instrument):
         """groove_bank_sample_channels: 1 (mono bank) or 2 (stereo bank)."""
         return self.ctx.L.groove_bank_sample_channels(self.h)
 
+    @property
+    def sample_interpolation(self):
+        """groove_bank_sample_interpolation: abi_types.SAMPLE_NEAREST (the default), SAMPLE_LINEAR or SAMPLE_CUBIC."""
+        return self.ctx.L.groove_bank_sample_interpolation(self.h)
+
+    @sample_interpolation.setter
+    def sample_interpolation(self, mode):
+        """groove_bank_set_sample_interpolation: from the next render on; parameters and state stay as they are."""
+        _lib.check(self.ctx.L.groove_bank_set_sample_interpolation(self.h, mode), self.ctx.h)
+
 
 class Effect:
     """IsEffect: TransformsAudio per lane over a block."""

@@ -521,6 +521,12 @@ int Orchestrator::set_wet_reverb_run(bool on) {
   return 0;
 }
 bool Orchestrator::wet_reverb_run() const { return groove_fx_wet_reverb_run(ctx_) != 0; }
+int Orchestrator::set_sample_interpolation(uint32_t mode) {
+  if (mode != GROOVE_SAMPLE_NEAREST && mode != GROOVE_SAMPLE_LINEAR && mode != GROOVE_SAMPLE_CUBIC)
+    return fail("set_sample_interpolation: unknown mode (0 nearest, 1 linear, 2 cubic)");
+  sample_interpolation_ = mode;
+  return 0;
+}
 int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units, bool on_instrument) {
   if (deferring_ && !on_instrument) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
   if (trip_units ? groove_ctl_trip_apply(link, at) : groove_ctl_link_apply(link, at)) return fail(groove_last_error(ctx_));
@@ -750,6 +756,12 @@ int gh_add_fm(void* h, const groove_fm_params* patch, uint32_t voices) {
   if (groove_fm_create(o->ctx(), p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
   return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::FM, voices, true, patch->carrier_envelope.release, false)));
 }
+// Orchestrator::set_sample_interpolation onto a sampler or drumkit bank just created (nothing to do for the default).
+static int apply_sample_interpolation(Orchestrator* o, groove_bank* b) {
+  if (o->sample_interpolation() == GROOVE_SAMPLE_NEAREST) return 0;
+  if (groove_bank_set_sample_interpolation(b, o->sample_interpolation())) { o->fail(groove_last_error(o->ctx())); groove_bank_destroy(b); return -1; }
+  return 0;
+}
 // Drumkit: one one-shot voice per sample buffer; MIDI key k plays buffer key_to_sample[k] (-1: none).  stereo: pcm is [frames][2],
 // interleaved left, right (groove_sampler_create_stereo).
 static int add_drumkit(void* h, bool stereo, const float* pcm, uint64_t frames, const groove_sample_desc* descs, uint32_t n_desc,
@@ -768,6 +780,7 @@ static int add_drumkit(void* h, bool stereo, const float* pcm, uint64_t frames, 
   groove_bank* b = nullptr;
   if (stereo ? groove_sampler_create_stereo(o->ctx(), pcm, frames, d.data(), n_desc, p.data(), 128, &b)
              : groove_sampler_create(o->ctx(), pcm, frames, d.data(), n_desc, p.data(), 128, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
+  if (apply_sample_interpolation(o, b)) return -1;
   struct Drumkit : VoiceBankInstrument {
     using VoiceBankInstrument::VoiceBankInstrument;
     void note_on(uint8_t key, uint8_t vel, uint64_t) override { groove_note_event e{key, key, vel, 1, 0}; groove_bank_note_events(bank(), &e, 1); }
@@ -782,7 +795,7 @@ int gh_add_drumkit_stereo(void* h, const float* pcm_lr, uint64_t frames, const g
   return add_drumkit(h, true, pcm_lr, frames, descs, n_desc, key_to_sample);
 }
 // Sampler (settings/src/instruments.rs:34-37, 81-88): one buffer (mono, or stereo: [frames][2] interleaved), `voices` voices that step
-// through it at note / root (no interpolation), stopped by their note-off.
+// through it at note / root (no interpolation, unless Orchestrator::set_sample_interpolation asks for it), stopped by their note-off.
 static int add_sampler(void* h, bool stereo, const char* who, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) {
   Orchestrator* o = (Orchestrator*)h;
   if (!pcm || !frames || !voices) { o->fail(std::string(who) + ": empty sample"); return -1; }
@@ -792,6 +805,7 @@ static int add_sampler(void* h, bool stereo, const char* who, const float* pcm, 
   groove_bank* b = nullptr;
   if (stereo ? groove_sampler_create_stereo(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)
              : groove_sampler_create(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
+  if (apply_sample_interpolation(o, b)) return -1;
   return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::SAMPLER, voices, true, 0.0, false)));
 }
 int gh_add_sampler(void* h, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) { return add_sampler(h, false, "gh_add_sampler", pcm, frames, root_hz, voices); }
@@ -838,6 +852,8 @@ void gh_set_wet_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_wet_l
 int gh_wet_links_on_device(void* h) { return ((Orchestrator*)h)->wet_links_on_device() ? 1 : 0; }
 void gh_set_stereo_samples(void* h, int on) { ((Orchestrator*)h)->set_stereo_samples(on != 0); }
 int gh_stereo_samples(void* h) { return ((Orchestrator*)h)->stereo_samples() ? 1 : 0; }
+int gh_set_sample_interpolation(void* h, uint32_t mode) { return ((Orchestrator*)h)->set_sample_interpolation(mode); }
+uint32_t gh_sample_interpolation(void* h) { return ((Orchestrator*)h)->sample_interpolation(); }
 int gh_set_wet_reverb_run(void* h, int on) { return ((Orchestrator*)h)->set_wet_reverb_run(on != 0); }
 int gh_wet_reverb_run(void* h) { return ((Orchestrator*)h)->wet_reverb_run() ? 1 : 0; }
 void gh_set_instrument_controls_on_device(void* h, int on) { ((Orchestrator*)h)->set_instrument_controls_on_device(on != 0); }

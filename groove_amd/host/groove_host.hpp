@@ -485,6 +485,11 @@ class Orchestrator {
   // upload.  Read when a project is instantiated (project.hpp instantiate).  Off by default: a stereo file is then the mean of its channels.
   void set_stereo_samples(bool on) { stereo_samples_ = on; }
   bool stereo_samples() const { return stereo_samples_; }
+  // How the sampler and drumkit banks added from here on read their samples between frames (groove_bank_set_sample_interpolation: a
+  // groove_sample_interpolation), every bank a project's instantiation creates among them.  GROOVE_SAMPLE_NEAREST by default: the
+  // reference's reading.  An unknown mode is refused (last_error) and changes nothing.
+  int set_sample_interpolation(uint32_t mode);
+  uint32_t sample_interpolation() const { return sample_interpolation_; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -532,6 +537,7 @@ class Orchestrator {
   bool wet_links_on_device_ = false;
   bool instrument_controls_on_device_ = false;
   bool stereo_samples_ = false;
+  uint32_t sample_interpolation_ = GROOVE_SAMPLE_NEAREST;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead
   bool ahead_eval_ = false;     // eval(): instruments already hold their block

@@ -27,6 +27,7 @@ def load():
         "gh_add_drumkit_stereo": (i, [vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), u32, C.POINTER(C.c_int)]),
         "gh_add_sampler": (i, [vp, _fp, C.c_uint64, d, u32]), "gh_add_sampler_stereo": (i, [vp, _fp, C.c_uint64, d, u32]),
         "gh_set_stereo_samples": (None, [vp, i]), "gh_stereo_samples": (i, [vp]),
+        "gh_set_sample_interpolation": (i, [vp, u32]), "gh_sample_interpolation": (u32, [vp]),
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
@@ -103,6 +104,14 @@ class Orchestrator:
         self.L.gh_set_stereo_samples(self.h, 1 if on else 0)
 
     def stereo_samples(self): return bool(self.L.gh_stereo_samples(self.h))
+
+    def set_sample_interpolation(self, mode):
+        """Sampler and drumkit banks added from here on (a project's among them) read their samples between frames by `mode`:
+        abi_types.SAMPLE_NEAREST (the default, the reference's reading), SAMPLE_LINEAR or SAMPLE_CUBIC.  An unknown mode raises."""
+        if self.L.gh_set_sample_interpolation(self.h, mode):
+            raise RuntimeError(self.L.gh_last_error(self.h).decode())
+
+    def sample_interpolation(self): return self.L.gh_sample_interpolation(self.h)
 
     def add_effect(self, kind, params): return self.L.gh_add_effect(self.h, kind, C.byref(params))
     def patch(self, source, sink): return self.L.gh_patch(self.h, source, sink)

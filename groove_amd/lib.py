@@ -65,6 +65,8 @@ SYMBOLS = {
     "groove_sampler_create": (_i, [_vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), _u32, C.POINTER(T.SamplerParams), _u32, _vpp]),
     "groove_sampler_create_stereo": (_i, [_vp, _fp, C.c_uint64, C.POINTER(T.SampleDesc), _u32, C.POINTER(T.SamplerParams), _u32, _vpp]),
     "groove_bank_sample_channels": (_u32, [_vp]),
+    "groove_bank_set_sample_interpolation": (_i, [_vp, _u32]),
+    "groove_bank_sample_interpolation": (_u32, [_vp]),
     "groove_bank_destroy": (_i, [_vp]),
     "groove_bank_voices": (_u32, [_vp]),
     "groove_bank_note_events": (_i, [_vp, C.POINTER(T.NoteEvent), _u32]),

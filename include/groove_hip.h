@@ -185,6 +185,19 @@ int groove_sampler_create_stereo(groove_ctx* ctx, const float* bank_pcm_lr, uint
                                  const groove_sampler_params* p, uint32_t n, groove_bank** out);
 /* Channels of a sampler bank's sample memory: 1 (groove_sampler_create) or 2 (groove_sampler_create_stereo); 0 for any other bank. */
 uint32_t groove_bank_sample_channels(groove_bank* bank);
+/* How a sampler or drumkit bank reads its sample BETWEEN frames (docs/DSP_SPEC.md section 7): a groove_sample_interpolation.
+ * GROOVE_SAMPLE_NEAREST (the default) plays pcm[floor(idx)] as the reference does; GROOVE_SAMPLE_LINEAR and GROOVE_SAMPLE_CUBIC
+ * (Catmull-Rom) weigh 2 and 4 frames around the cursor by the top 24 bits of its fraction, per channel on a stereo bank.  A tap before
+ * a sample's first or past its last frame is 0 and is never read from memory: neighbouring samples of the bank are not heard.  Only
+ * the value a frame plays changes: cursor, end rule, note rules, parameters and state are the same in every mode (the same events
+ * leave the same groove_bank_download_state words), and a voice whose step is an integer — a drumkit, a key on the root — plays
+ * NEAREST's bits.  The setter is refused with a message for a bank of another kind and for an unknown mode; it joins the bank's
+ * earlier work first, like groove_bank_set_param, may be called between any two renders and touches neither parameters nor state.
+ * Everything that takes a sampler bank takes an interpolated one (the four render entries, reset, a sample-rate change,
+ * groove_bank_set_param, links onto the gain); groove_bank_kernel_form names the mode after the form.  The getter reports
+ * GROOVE_SAMPLE_NEAREST for a bank of another kind. */
+int groove_bank_set_sample_interpolation(groove_bank* bank, uint32_t mode);
+uint32_t groove_bank_sample_interpolation(groove_bank* bank);
 int groove_bank_destroy(groove_bank* bank);
 uint32_t groove_bank_voices(groove_bank* bank);
 /* HandlesMidi::handle_midi_message → PlaysNotes::note_on/note_off (orchestrator.rs:737-739;
@@ -261,8 +274,9 @@ int groove_bank_render_mix_deferred(groove_bank* bank, uint32_t frames, float* b
  * deferred exactly as above (carried by the next such call, or flushed).  For projects with at most one time-parallel bank of each
  * kind and at most 2,048 partial rows in all (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096 sampler
  * voices, three launches whose durations added -> one); anything else is rendered bank by bank by groove_bank_render_mix_deferred in
- * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them always takes that bank-by-bank path (the one
- * launch's sampler body is the mono one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
+ * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them, or one whose sample
+ * interpolation is not GROOVE_SAMPLE_NEAREST, always takes that bank-by-bank path (the one launch's sampler body is the mono,
+ * nearest one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
  * the same bits (one reduction over all rows instead of one per bank).  No reference counterpart as a call: the reference ticks
  * every instrument inside gather_audio. */
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate);

@@ -197,6 +197,13 @@ typedef enum {
   GROOVE_CTL_SAMPLER_GAIN = 64       /* "gain": (float)clamp01(v)                        */
 } groove_control_index;
 
+/* How a sampler or drumkit bank reads its sample between frames (groove_bank_set_sample_interpolation; docs/DSP_SPEC.md section 7). */
+typedef enum {
+  GROOVE_SAMPLE_NEAREST = 0, /* pcm[floor(idx)]: the reference's reading, and the default                          */
+  GROOVE_SAMPLE_LINEAR = 1,  /* two taps                                                                            */
+  GROOVE_SAMPLE_CUBIC = 2    /* four taps, Catmull-Rom                                                              */
+} groove_sample_interpolation;
+
 /* Controller devices (the schema's third device class, settings/src/controllers.rs: "lfo", "signal-passthrough-controller")
  * as the SOURCE of a control link, groove_ctl_link_create.  docs/DSP_SPEC.md section 13 defines the value laws. */
 typedef enum {
