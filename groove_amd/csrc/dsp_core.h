@@ -42,14 +42,14 @@ namespace groove {
 // ------------------------------------------------------------------ small math
 GROOVE_HD float fast_exp2(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_exp2f(x); // v_exp_f32
+  return __builtin_amdgcn_exp2f(x); // v_exp_f32: 1 ulp on [-16, 16] (tests/test_gpu_dsp_primitives.py::test_fast_exp2_within_one_ulp)
 #else
   return exp2f(x);
 #endif
 }
 GROOVE_HD float fast_rcp(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  // v_rcp_f32: 1 ulp.  (A Newton step on top changed neither the worst nor the median per-voice error
+  // v_rcp_f32: 1 ulp (tests/test_gpu_dsp_primitives.py::test_fast_rcp_within_one_ulp).  (A Newton step on top changed neither the worst nor the median per-voice error
   // against the oracle — tools/gpu_error.py: 2.571e-6 / 1.1e-7 either way — and cost 1.5 % of a block.)
   return __builtin_amdgcn_rcpf(x);
 #else
@@ -61,8 +61,9 @@ GROOVE_HD float fast_rcp(float x) {
 GROOVE_HD float sin_turns_folded(float x) {
   const float y = x * 6.283185307179586f;
   const float y2 = y * y;
-  float p = 2.5992782e-06f;            // least-squares fit on Chebyshev nodes, |y| <= pi/2:
-  p = fmaf(p, y2, -1.9806202e-04f);    // max abs error 1.0e-7 in fp32 (tests/test_emul.py)
+  float p = 2.5992782e-06f;            // least-squares fit on Chebyshev nodes, |y| <= pi/2: max abs error 1.28e-7 in fp32, at
+  p = fmaf(p, y2, -1.9806202e-04f);    // x = -0.24997938 turns (tests/test_dsp_primitives_cpu.py::test_sin_turns_folded_fp32_error:
+                                       // 2^22 phases; 7e-9 of it is the fit, the rest fp32 roundings of y and of a result next to 1, ulp 6e-8)
   p = fmaf(p, y2, 8.3330103e-03f);
   p = fmaf(p, y2, -1.6666657e-01f);
   return fmaf(p * y2, y, y);
@@ -92,7 +93,7 @@ GROOVE_HD int64_t fold_quarter64(int64_t q) {
   if ((q ^ (q << 1)) < 0) q = (int64_t)(0x8000000000000000ull - (uint64_t)q);
   return q;
 }
-// 2^x for |x| <= 1 in f64 (Taylor in x ln2, 1e-14 relative).
+// 2^x for |x| <= 1 in f64 (Taylor in x ln2, 1e-14 relative: tests/test_dsp_primitives_cpu.py::test_exp2_small_f64_error measures 6.3e-15).
 GROOVE_HD double exp2_small_f64(double x) {
   const double t = x * 0.693147180559945309417;
   double p = 1.14707455977297247139e-11; // 1/14!
@@ -111,7 +112,8 @@ GROOVE_HD double exp2_small_f64(double x) {
   p = fma(p, t, 1.0);
   return fma(p, t, 1.0);
 }
-// e^x for |x| <= 1.5e-3 (x^5/120 < 1e-16): the per-frame growth factor of a slowly moving exponent.
+// e^x for |x| <= 1.5e-3 (x^5/120 < 1e-16; 1.7e-16 relative with the roundings, tests/test_dsp_primitives_cpu.py::test_exp_tiny_f64_error):
+// the per-frame growth factor of a slowly moving exponent.
 GROOVE_HD double exp_tiny_f64(double x) {
   double p = 4.16666666666666666667e-02;
   p = fma(p, x, 1.66666666666666666667e-01);
@@ -123,7 +125,8 @@ GROOVE_HD double exp_tiny_f64(double x) {
 // hi = (x > pi/4), i.e. tan(x) = hi ? 1/t : t.  The caller keeps working with t (never forms
 // 1/t), which is what keeps the filter coefficients accurate next to Nyquist.
 // tan(z) = z P(z^2) on [0, pi/4]: weighted least squares on Chebyshev nodes for the RELATIVE error
-// (the coefficient formulas need t to a relative accuracy); max relative error 1.5e-7 in fp32, the
+// (the coefficient formulas need t to a relative accuracy); max relative error 1.5e-7 in fp32
+// (tests/test_dsp_primitives_cpu.py::test_tan_of_reduced_relative_error: 1.41e-7 over 2^16 mantissas a binade), the
 // same as the sin / cos quotient it replaces, in 8 instructions instead of 14 and no reciprocal.
 GROOVE_HD float tan_of_reduced(float z);
 GROOVE_HD float tan_reduced(float x, bool& hi) {
@@ -144,7 +147,8 @@ GROOVE_HD float tan_of_reduced(float z) {
 GROOVE_HD float clamp01f(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 GROOVE_HD double clamp01d(double x) { return fmin(fmax(x, 0.0), 1.0); }
 
-// f64 -> u64 (truncating) for 0 <= x < 2^64
+// f64 -> u64 (truncating) for 0 <= x < 2^64.  (This and every other device-only branch of this file is run by itself, against the C beside
+// it and against exact references, by tests/probe and tests/test_gpu_dsp_primitives.py.)
 GROOVE_HD uint64_t f64_to_u64(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // two v_cvt_u32_f64 (truncating) around one exact fma: hi = floor(x / 2^32), lo = x - hi * 2^32
@@ -155,12 +159,6 @@ GROOVE_HD uint64_t f64_to_u64(double x) {
 #else
   return (uint64_t)x;
 #endif
-}
-// turns (f64, any sign, |x| < 2^31) -> wrapped 64-bit phase increment
-GROOVE_HD uint64_t turns_to_phase(double turns) {
-  double fl = floor(turns);
-  double frac = turns - fl; // [0,1)
-  return (uint64_t)(frac * 18446744073709551616.0);
 }
 // signed increment: turns may be negative (FM through zero); two's complement add.  Whole turns drop out (the oracle's pos -= floor(pos)):
 // an FM index of 100 on A4 — the reference's own demo project — swings the carrier past a whole turn per frame, and a u64 conversion of
@@ -176,6 +174,9 @@ GROOVE_HD uint64_t turns_to_inc(double turns) {
   if (turns >= 0.0) return (uint64_t)(fract_f64(turns) * 18446744073709551616.0);
   return (uint64_t)0 - (uint64_t)(fract_f64(-turns) * 18446744073709551616.0);
 }
+// turns (f64, any sign, |x| < 2^31) -> wrapped 64-bit phase: the same wrap.  (Until tests/test_dsp_primitives_cpu.py it formed
+// turns - floor(turns) in one subtraction, which rounds to 1.0 for -2^-54 < turns < 0 — and 2^64 has no u64.  No caller was affected.)
+GROOVE_HD uint64_t turns_to_phase(double turns) { return turns_to_inc(turns); }
 
 // ------------------------------------------------------------------ Oscillator (a1)
 struct OscState {

@@ -14,7 +14,9 @@ def build():
     out = os.path.join(HERE, "libemul.so")
     deps = [src] + [os.path.join(HERE, "..", "..", "groove_amd", "csrc", f) for f in ("dsp_core.h", "derive.h", "welsh_tp.h", "welsh_split.h")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        # -ffp-contract=off: fmaf() calls stay fused, plain a*b+c stays unfused, like hipcc's default for explicit code
+        # -ffp-contract=off: fmaf() calls stay fused, plain a*b+c stays unfused.  The DEVICE build contracts (hipcc's default: a*b+c becomes
+        # one v_fma unless the function says GROOVE_NO_CONTRACT), so this build is a neighbour of the device arithmetic, not the thing
+        # itself: tests/test_gpu_dsp_primitives.py (sections d and e) measures the distance, docs/DSP_SPEC.md section 14 records it
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src], check=True)
     return out
 
