@@ -66,6 +66,11 @@ class SampleDesc(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("root_hz", C.c_float)]
 
 
+class SampleLoop(C.Structure):
+    """groove_sample_loop: frames inside the sample, [start, end); 0, 0: none."""
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32)]
+
+
 class SamplerParams(C.Structure):
     _fields_ = [("sample_index", C.c_uint32), ("one_shot", C.c_uint32), ("gain", C.c_float)]
 

@@ -1555,6 +1555,151 @@ GROOVE_HD void sampler_chunk_interp_stereo(const SamplerParams& p, SamplerState&
   if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
 }
 
+// FORWARD LOOPS (groove_bank_set_sample_loops; docs/DSP_SPEC.md section 7): a bank property like the mode.  A sample may carry one loop
+// [start, end), in frames from its first frame, 0 <= start < end <= length; 0, 0: none.  With S = start << 44, E = end << 44 and
+// L = E - S the cursor of a looping voice is FOLDED, F(x) = x below E and S + (x - S) mod L from there on, in exact 64-bit integers:
+// the frame is read at c = F(idx) and leaves idx = F(c + step), so c < E <= length << 44 and the end rule is never met.  F(F(x) + y) =
+// F(x + y): frame f of a block is read at F(idx + f * step) whatever the split into blocks.  S, E and L are multiples of 2^44, so the
+// 64-bit modulo is a 32-bit one on the frame number and the fraction passes through.
+struct SampleLoop { uint32_t start, end; };
+constexpr uint64_t kSampleFracMask = (1ull << 44) - 1;
+// Which voices loop: the sample has a loop, the voice is no one-shot (a drumkit voice ignores note-off and would never end) and plays.
+GROOVE_HD bool sampler_voice_loops(const SamplerParams& p, const SamplerState& s, const SampleLoop& lp) { return lp.end != 0 && !p.one_shot && s.playing; }
+GROOVE_HD uint64_t sample_loop_wrap(uint64_t y, uint32_t start, uint32_t end) { // S + y mod L  (y >> 44 < 2^20)
+  return ((uint64_t)(start + (uint32_t)(y >> 44) % (end - start)) << 44) | (y & kSampleFracMask);
+}
+GROOVE_HD uint64_t sample_loop_fold(uint64_t x, uint32_t start, uint32_t end) { // F(x)
+  return x < ((uint64_t)end << 44) ? x : sample_loop_wrap(x - ((uint64_t)start << 44), start, end);
+}
+// F(c + a) for a folded c (c < E).  c + a may pass 2^64 (length < 2^20, so E < 2^64 - 2^44, and a high key's step is large): the sum is
+// never formed — a frame that stays below E has a < E - c, and one that does not lies at S + (a - (E - c)) mod L.
+GROOVE_HD uint64_t sample_loop_advance(uint64_t c, uint64_t a, uint32_t start, uint32_t end) {
+  const uint64_t room = ((uint64_t)end << 44) - c;
+  return a < room ? c + a : sample_loop_wrap(a - room, start, end);
+}
+// Tap j = i + k of a looping voice (i < end).  j >= end is read at start + (j - start) mod (end - start): the seam is read as the loop
+// repeats — loops of 1, 2 or 3 frames are shorter than CUBIC's reach.  j - end <= 1 (k <= 2) is below twice the loop's length, so
+// one conditional subtraction is the modulo.  j < 0 (returned as it is) is silence, 0 <= j < start the frame that lies there: no tap
+// of a looping voice is outside [0, end).
+GROOVE_HD int32_t sample_loop_tap(uint32_t i, int k, uint32_t start, uint32_t end) {
+  const int32_t j = (int32_t)i + k;
+  if (j < (int32_t)end) return j;
+  const uint32_t lam = end - start, d = (uint32_t)j - end;
+  return (int32_t)(start + (d >= lam ? d - lam : d));
+}
+// The address (never outside the sample) and the select of tap i + k for a voice that loops (end != 0) or does not (end == 0: the
+// rule of sample_tap_clamped / sample_tap_inside, word for word).
+GROOVE_HD uint32_t sample_loop_tap_clamped(uint32_t i, int k, uint32_t length, uint32_t start, uint32_t end) {
+  if (!end) return sample_tap_clamped(i, k, length);
+  const int32_t j = sample_loop_tap(i, k, start, end);
+  return j < 0 ? 0u : (uint32_t)j;
+}
+GROOVE_HD bool sample_loop_tap_inside(uint32_t i, int k, uint32_t length, uint32_t end) { return end ? (int32_t)i + k >= 0 : sample_tap_inside(i, k, length); }
+// Where frame f of a chunk is read: c the cursor at its first frame (folded if the voice loops), a = f * step.
+GROOVE_HD uint64_t sample_loop_pos(uint64_t c, uint64_t a, uint32_t start, uint32_t end) { return end ? sample_loop_advance(c, a, start, end) : c + a; }
+// The per-frame DEFINITION on a bank with loops, mono and stereo, every mode.  A voice that does not loop is sampler_frame_interp's.
+template <int MODE>
+GROOVE_HD float sampler_frame_loop(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const float* bank) {
+  using T = SampleTaps<MODE>;
+  if (!sampler_voice_loops(p, s, lp)) return sampler_frame_interp<MODE>(p, s, bank);
+  const uint64_t c = sample_loop_fold(s.idx, lp.start, lp.end);
+  const uint32_t i = (uint32_t)(c >> 44);
+  float q[T::N];
+  for (int m = 0; m < T::N; ++m) {
+    const int32_t j = sample_loop_tap(i, T::FIRST + m, lp.start, lp.end);
+    q[m] = j >= 0 ? bank[(size_t)p.offset + (uint32_t)j] : 0.0f;
+  }
+  const float v = sample_interp<MODE>(q, sample_fraction(c)) * p.gain;
+  s.idx = sample_loop_advance(c, s.step, lp.start, lp.end);
+  return v;
+}
+template <int MODE>
+GROOVE_HD void sampler_frame_loop_stereo(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const SamplePair* bank, float& L, float& R) {
+  using T = SampleTaps<MODE>;
+  if (!sampler_voice_loops(p, s, lp)) { sampler_frame_interp_stereo<MODE>(p, s, bank, L, R); return; }
+  const uint64_t c = sample_loop_fold(s.idx, lp.start, lp.end);
+  const uint32_t i = (uint32_t)(c >> 44);
+  float ql[T::N], qr[T::N];
+  for (int m = 0; m < T::N; ++m) {
+    const int32_t j = sample_loop_tap(i, T::FIRST + m, lp.start, lp.end);
+    ql[m] = qr[m] = 0.0f;
+    if (j >= 0) { const SamplePair x = bank[(size_t)p.offset + (uint32_t)j]; ql[m] = x.l; qr[m] = x.r; }
+  }
+  const float t = sample_fraction(c);
+  L = sample_interp<MODE>(ql, t) * p.gain;
+  R = sample_interp<MODE>(qr, t) * p.gain;
+  s.idx = sample_loop_advance(c, s.step, lp.start, lp.end);
+}
+// sampler_chunk_interp / sampler_chunk_interp_stereo on a bank with loops: one text for the voices that loop and those that do not
+// (lanes of one wavefront are voices of both kinds), frame k at its closed-form position, all C * N fetches issued before any is used.
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_loop(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const float* bank, uint32_t count, float (&v)[C]) {
+  using T = SampleTaps<MODE>;
+  const bool loops = sampler_voice_loops(p, s, lp);
+  const uint32_t ls = loops ? lp.start : 0u, le = loops ? lp.end : 0u;
+  const uint64_t c0 = loops ? sample_loop_fold(s.idx, ls, le) : s.idx;
+  uint32_t valid = 0; // frames of the chunk that play (a looping voice: all `count`)
+  float raw[C][T::N];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint32_t i = (uint32_t)(sample_loop_pos(c0, (uint64_t)k * s.step, ls, le) >> 44);
+    const bool ok = s.playing && (uint32_t)k < count && i < p.length;
+    const uint32_t ic = i < p.length ? i : p.length - 1;
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) raw[k][m] = bank[(size_t)p.offset + sample_loop_tap_clamped(ic, T::FIRST + m, p.length, ls, le)];
+    valid += ok ? 1u : 0u;
+    v[k] = ok ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint64_t pos = sample_loop_pos(c0, (uint64_t)k * s.step, ls, le);
+    const uint32_t i = (uint32_t)(pos >> 44);
+    float q[T::N];
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) q[m] = sample_loop_tap_inside(i, T::FIRST + m, p.length, le) ? raw[k][m] : 0.0f;
+    v[k] = v[k] != 0.0f ? sample_interp<MODE>(q, sample_fraction(pos)) * p.gain : 0.0f;
+  }
+  if (count) s.idx = sample_loop_pos(c0, (uint64_t)valid * s.step, ls, le); // (no frame: the cursor is not folded either)
+  if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+}
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_loop_stereo(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) {
+  using T = SampleTaps<MODE>;
+  const bool loops = sampler_voice_loops(p, s, lp);
+  const uint32_t ls = loops ? lp.start : 0u, le = loops ? lp.end : 0u;
+  const uint64_t c0 = loops ? sample_loop_fold(s.idx, ls, le) : s.idx;
+  uint32_t valid = 0; // frames of the chunk that play (a looping voice: all `count`)
+  SamplePair raw[C][T::N];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint32_t i = (uint32_t)(sample_loop_pos(c0, (uint64_t)k * s.step, ls, le) >> 44);
+    const bool ok = s.playing && (uint32_t)k < count && i < p.length;
+    const uint32_t ic = i < p.length ? i : p.length - 1;
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) raw[k][m] = bank[(size_t)p.offset + sample_loop_tap_clamped(ic, T::FIRST + m, p.length, ls, le)];
+    valid += ok ? 1u : 0u;
+    l[k] = ok ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    const uint64_t pos = sample_loop_pos(c0, (uint64_t)k * s.step, ls, le);
+    const uint32_t i = (uint32_t)(pos >> 44);
+    const bool ok = l[k] != 0.0f;
+    float ql[T::N], qr[T::N];
+#pragma unroll
+    for (int m = 0; m < T::N; ++m) {
+      const bool in = sample_loop_tap_inside(i, T::FIRST + m, p.length, le);
+      ql[m] = in ? raw[k][m].l : 0.0f;
+      qr[m] = in ? raw[k][m].r : 0.0f;
+    }
+    const float t = sample_fraction(pos);
+    l[k] = ok ? sample_interp<MODE>(ql, t) * p.gain : 0.0f;
+    r[k] = ok ? sample_interp<MODE>(qr, t) * p.gain : 0.0f;
+  }
+  if (count) s.idx = sample_loop_pos(c0, (uint64_t)valid * s.step, ls, le); // (no frame: the cursor is not folded either)
+  if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+}
+
 // ------------------------------------------------------------------ effects (a8, a9)
 GROOVE_HD float bitcrush(float x, uint32_t bits) {
   float ax = fabsf(x) * 32767.0f;

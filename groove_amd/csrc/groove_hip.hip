@@ -128,6 +128,11 @@ struct groove_bank {
   float* d_pcm = nullptr;   // sampler bank: [bank_frames] values, or [bank_frames] interleaved left, right pairs ...
   bool pcm_stereo = false;  // ... of a stereo bank (groove_sampler_create_stereo): picks the kernels' STEREO instantiations
   uint32_t pcm_interp = GROOVE_SAMPLE_NEAREST; // sampler bank: a groove_sample_interpolation, read at every launch (picks the kernels' MODE instantiations)
+  // sampler bank: the samples' forward loops (groove_bank_set_sample_loops; empty: never set), whether any sample has one (picks the
+  // kernels' LOOP instantiations) and, allocated with the first loop, each VOICE's loop words [2][n] — start row, end row, its sample's
+  std::vector<groove_sample_loop> loops;
+  bool looped = false;
+  uint32_t* d_loops = nullptr;
   // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
   // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
   // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one).  fm: the same owner with CTL_FM_WORDS rows — gain, pan, depth,
@@ -1578,6 +1583,51 @@ int groove_bank_set_sample_interpolation(groove_bank* b, uint32_t mode) {
   return 0;
 }
 uint32_t groove_bank_sample_interpolation(groove_bank* b) { return b && b->kind == BANK_SAMPLER ? b->pcm_interp : (uint32_t)GROOVE_SAMPLE_NEAREST; }
+// Like the mode a property of the bank beside parameters and state: reset, a sample-rate change and groove_bank_set_param upload the
+// records and leave d_loops alone.  The kernels read a voice's loop by its index, so the samples' loops are spread over the voices here.
+int groove_bank_set_sample_loops(groove_bank* b, const groove_sample_loop* loops, uint32_t n_samples) {
+  if (!b) return fail(nullptr, "groove_bank_set_sample_loops: bank is NULL");
+  groove_ctx* ctx = b->ctx;
+  if (b->kind != BANK_SAMPLER) return fail(ctx, "groove_bank_set_sample_loops: only sampler and drumkit banks play samples");
+  if (loops) {
+    if (n_samples != b->descs.size()) return fail(ctx, "groove_bank_set_sample_loops: n_samples is not the bank's sample count (" + std::to_string(b->descs.size()) + ")");
+    for (uint32_t i = 0; i < n_samples; ++i) {
+      if (loops[i].start == 0 && loops[i].end == 0) continue;
+      if (loops[i].start >= loops[i].end) return fail(ctx, "groove_bank_set_sample_loops: start >= end (sample " + std::to_string(i) + ")");
+      if (loops[i].end > b->descs[i].length) return fail(ctx, "groove_bank_set_sample_loops: end beyond the sample's length (sample " + std::to_string(i) + ")");
+    }
+  }
+  if (ctx_join(ctx)) return 1;
+  bool any = false;
+  for (uint32_t i = 0; loops && i < n_samples; ++i) any = any || loops[i].end != 0;
+  if (any) {
+    const uint32_t n = b->n;
+    std::vector<uint32_t> w((size_t)2 * n);
+    for (uint32_t v = 0; v < n; ++v) {
+      const groove_sample_loop& l = loops[b->sampler[v].sample_index];
+      w[v] = l.start; w[(size_t)n + v] = l.end;
+    }
+    GHIP(ctx, hipSetDevice(ctx->device));
+    GHIP(ctx, ctx_wait(ctx)); // (the last launch that read d_loops has finished)
+    if (!b->d_loops && hipMalloc(&b->d_loops, w.size() * 4) != hipSuccess) { b->d_loops = nullptr; return fail(ctx, "groove_bank_set_sample_loops: hipMalloc failed"); }
+    GHIP(ctx, ctx_memcpy(ctx, b->d_loops, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    b->loops.assign(loops, loops + n_samples);
+  } else {
+    b->loops.clear();
+  }
+  b->looped = any;
+  return 0;
+}
+uint32_t groove_bank_sample_loops(groove_bank* b, groove_sample_loop* out, uint32_t cap) {
+  if (!b || b->kind != BANK_SAMPLER) return 0;
+  uint32_t looped = 0;
+  for (size_t i = 0; i < b->descs.size(); ++i) {
+    const groove_sample_loop l = i < b->loops.size() ? b->loops[i] : groove_sample_loop{0, 0};
+    if (out && i < cap) out[i] = l;
+    looped += l.end != 0;
+  }
+  return looped;
+}
 int groove_bank_destroy(groove_bank* b) {
   if (!b) return 0;
   groove_ctx* ctx = b->ctx;
@@ -1595,7 +1645,7 @@ int groove_bank_destroy(groove_bank* b) {
     if (l->bank == b) l->bank = nullptr;
   (void)hipFree(b->d_dca);
   for (int k = 0; k < 2; ++k) { if (b->h_ev[k]) (void)hipHostFree(b->h_ev[k]); if (b->ev_staged[k]) (void)hipEventDestroy(b->ev_staged[k]); }
-  (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
+  (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_loops); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
   delete b;
   return 0;
 }
@@ -1788,14 +1838,20 @@ static void launch_small_uniform(const groove_bank* b, const UniformArgs& a, hip
     launch_welsh_kind(k, r, st, fused, (k == 5 || !p.count[5]) ? done : nullptr);
   }
 }
-// The serial sampler kernel of an interpolated bank (MODE LINEAR or CUBIC).
-extern "C++" template <int MODE>
-static void launch_sampler_serial_interp(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
+// The serial sampler kernel: one mode, with or without looped samples (LOOP: b->d_loops, the voices' loop words).
+extern "C++" template <int MODE, bool LOOP>
+static void launch_sampler_serial_form(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
+  const uint32_t* loops = LOOP ? b->d_loops : nullptr;
   if (b->pcm_stereo) {
-    if (fused) launch_bound(sampler_render_kernel<true, true, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-    else launch_bound(sampler_render_kernel<false, true, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-  } else if (fused) launch_bound(sampler_render_kernel<true, false, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-  else launch_bound(sampler_render_kernel<false, false, MODE>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+    if (fused) launch_bound(sampler_render_kernel<true, true, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
+    else launch_bound(sampler_render_kernel<false, true, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
+  } else if (fused) launch_bound(sampler_render_kernel<true, false, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
+  else launch_bound(sampler_render_kernel<false, false, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
+}
+extern "C++" template <int MODE>
+static void launch_sampler_serial_mode(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
+  if (b->looped) launch_sampler_serial_form<MODE, true>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+  else launch_sampler_serial_form<MODE, false>(b, frames, fused, chs, out, rows, grid, blk, st, done);
 }
 // Every form but the big uniform one is ONE launch sequence on ONE stream, and this is where it is launched.  fused: `rows` =
 // partial rows only; otherwise `out` = the planar block and `rows` = its row sums (kernels.h run_frames), null for none.
@@ -1812,7 +1868,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (prev) a.prev = *prev;
       if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
       if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
-      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->pcm_interp, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
+      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->pcm_interp, b->looped ? b->d_loops : nullptr, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
       else { a.full_coef = b->plan.tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
       break;
     }
@@ -1831,13 +1887,9 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       else launch_bound(fm_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows);
       break;
     case Form::SamplerSerial:
-      if (b->pcm_interp == GROOVE_SAMPLE_LINEAR) launch_sampler_serial_interp<GROOVE_SAMPLE_LINEAR>(b, frames, fused, chs, out, rows, grid, blk, st, done);
-      else if (b->pcm_interp == GROOVE_SAMPLE_CUBIC) launch_sampler_serial_interp<GROOVE_SAMPLE_CUBIC>(b, frames, fused, chs, out, rows, grid, blk, st, done);
-      else if (b->pcm_stereo) {
-        if (fused) launch_bound(sampler_render_kernel<true, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-        else launch_bound(sampler_render_kernel<false, true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-      } else if (fused) launch_bound(sampler_render_kernel<true>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
-      else launch_bound(sampler_render_kernel<false>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm);
+      if (b->pcm_interp == GROOVE_SAMPLE_LINEAR) launch_sampler_serial_mode<GROOVE_SAMPLE_LINEAR>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+      else if (b->pcm_interp == GROOVE_SAMPLE_CUBIC) launch_sampler_serial_mode<GROOVE_SAMPLE_CUBIC>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+      else launch_sampler_serial_mode<GROOVE_SAMPLE_NEAREST>(b, frames, fused, chs, out, rows, grid, blk, st, done);
       break;
     case Form::WelshBigUniform: break; // (the callers' own walks over big_pieces / the base kinds: their stream policies differ on purpose)
   }
@@ -2215,7 +2267,7 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
 // groove_bank_render_mix_deferred for SEVERAL small banks of different kinds at once: ONE launch for the whole block (welsh_tp.h
 // tp_mixed_kernel: a grid whose workgroups dispatch on their index into the Welsh / FM / sampler time-parallel bodies), one row
 // buffer, one carried reduction — Orchestrator::gather_audio's one sum over all instruments (orchestrator.rs:397-410).  Takes
-// projects with at most one time-parallel bank of each kind, no stereo or interpolated sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
+// projects with at most one time-parallel bank of each kind, no stereo, interpolated or looped sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
 // through groove_bank_render_mix_deferred, in the order given.
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate) {
   if (!ctx || !bus_dev || (n_banks && !banks)) return fail(ctx, "groove_banks_render_mix_deferred: NULL argument");
@@ -2232,7 +2284,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
     if (!b) return fail(ctx, "groove_banks_render_mix_deferred: NULL bank");
     if (b->ctx != ctx) return fail(ctx, "groove_banks_render_mix_deferred: a bank of another ctx");
     const int k = b->kind == BANK_WELSH ? 0 : b->kind == BANK_FM ? 1 : 2;
-    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo || b->pcm_interp != GROOVE_SAMPLE_NEAREST) ok = false; // (tp_mixed_kernel's sampler body is the mono, nearest one)
+    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo || b->pcm_interp != GROOVE_SAMPLE_NEAREST || b->looped) ok = false; // (tp_mixed_kernel's sampler body is the mono, nearest, loop-free one)
     of_kind[k] = b;
   }
   TpMixedArgs m{};
@@ -2319,10 +2371,16 @@ const char* groove_bank_kernel_form(groove_bank* b, uint32_t frames, int fused) 
     case Form::TimeParallel:
       if (b->kind == BANK_WELSH) return tp_vpw(b) == 2 ? "welsh_tp_kernel (time-parallel, two voices per wavefront)" : "welsh_tp_kernel (time-parallel, one wavefront per voice)";
       if (b->kind == BANK_FM) return tp_vpw(b) == 4 ? "fm_tp_kernel (time-parallel, four voices per wavefront)" : "fm_tp_kernel (time-parallel)";
+      if (b->looped)
+        return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_tp_kernel (time-parallel, linear interpolation, looped)"
+             : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_tp_kernel (time-parallel, cubic interpolation, looped)" : "sampler_tp_kernel (time-parallel, looped)";
       return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_tp_kernel (time-parallel, linear interpolation)"
            : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_tp_kernel (time-parallel, cubic interpolation)" : "sampler_tp_kernel (time-parallel)";
     case Form::FmSerial: return "fm_render_kernel (serial, one voice per lane)";
     case Form::SamplerSerial:
+      if (b->looped)
+        return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_render_kernel (serial, one voice per lane, linear interpolation, looped)"
+             : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_render_kernel (serial, one voice per lane, cubic interpolation, looped)" : "sampler_render_kernel (serial, one voice per lane, looped)";
       return b->pcm_interp == GROOVE_SAMPLE_LINEAR ? "sampler_render_kernel (serial, one voice per lane, linear interpolation)"
            : b->pcm_interp == GROOVE_SAMPLE_CUBIC ? "sampler_render_kernel (serial, one voice per lane, cubic interpolation)" : "sampler_render_kernel (serial, one voice per lane)";
     case Form::WelshPerLane: return "welsh_render_kernel (per-lane parameters)";

@@ -875,15 +875,19 @@ __global__ __launch_bounds__(kThreads) void fm_render_kernel(
 // MODE (groove_sample_interpolation): LINEAR and CUBIC read 2 and 4 taps per frame (dsp_core.h sampler_chunk_interp: 16 * N fetches in
 // flight); the NEAREST instantiations are the text they were.  CUBIC STEREO holds 16 * 4 * 2 = 128 fetched values: 220 VGPRs of
 // the 512 a 256-thread workgroup may use, no scratch (the compiler's resource table), so the chunk stays 16 frames in every instantiation.
-template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
+// LOOP (groove_bank_set_sample_loops): a bank with a looped sample.  `loops` holds each voice's SampleLoop, [2][n] like the records
+// (start row, end row; 0, 0 for a voice whose sample has none), and only these instantiations read it: the others are the text they were.
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
 __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n, uint32_t frames,
-    size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank) {
+    size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank, const uint32_t* __restrict__ loops) {
   const uint32_t v0 = blockIdx.x * kThreads + threadIdx.x;
   const bool active = v0 < n;
   const uint32_t v = active ? v0 : n - 1;
   const SamplerParams p = soa_load<SamplerParams>(params, n, v);
   SamplerState s = soa_load<SamplerState>(state, n, v);
+  SampleLoop lp{0, 0};
+  if constexpr (LOOP) lp = soa_load<SampleLoop>(loops, n, v);
   // chunks of 16 frames: sixteen fetches in flight instead of one (sampler_chunk); mono duplicated to both channels
   constexpr uint32_t C = 16, K = FusedAcc::kChunk;
   static_assert(C % K == 0, "whole flush periods of the fused epilogue per chunk");
@@ -892,7 +896,10 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t count = min(C, frames - f0);
     float x[C];
     float xr[STEREO ? C : 1]; // (a stereo bank's right channel; a mono voice is duplicated to both channels)
-    if constexpr (MODE != GROOVE_SAMPLE_NEAREST) {
+    if constexpr (LOOP) {
+      if constexpr (STEREO) sampler_chunk_loop_stereo<MODE, C>(p, lp, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
+      else sampler_chunk_loop<MODE, C>(p, lp, s, bank, count, x);
+    } else if constexpr (MODE != GROOVE_SAMPLE_NEAREST) {
       if constexpr (STEREO) sampler_chunk_interp_stereo<MODE, C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
       else sampler_chunk_interp<MODE, C>(p, s, bank, count, x);
     } else if constexpr (STEREO) sampler_chunk_stereo<C>(p, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);

@@ -875,8 +875,14 @@ template <int WAVES> struct SamplerTpSmem<WAVES, true> { // a stereo bank: the l
 // two tiles; each channel's sum is taken in the order the mono sum is (voice order within a wave, wave order within the workgroup).
 // MODE (groove_sample_interpolation): LINEAR and CUBIC fetch a frame's 2 or 4 taps (dsp_core.h SampleTaps, sample_interp) where NEAREST
 // fetches one value; `valid`, ok[][] and the state are the same in every mode, and the NEAREST instantiations are the text they were.
-template <bool FUSED, int WAVES, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
-__device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES, STEREO>& sm) {
+// LOOP (groove_bank_set_sample_loops): a bank with a looped sample; `loops` = each voice's SampleLoop, [2][n] (kernels.h
+// sampler_render_kernel), read by these instantiations only.  A looping voice's cursor is folded once, lane-parallel, after the
+// block's note events; its `valid` is the whole block, frame f is read at the closed form F(idx + f * step) (dsp_core.h
+// sample_loop_advance: a 32-bit modulo on the frame number, the 64-bit sum never formed) and the state it stores is F(idx + frames * step).
+// Whether a voice loops is wave-uniform in the gather (one voice at a time): the fold is a uniform branch.
+template <bool FUSED, int WAVES, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
+__device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES, STEREO>& sm,
+                                                const uint32_t* __restrict__ loops = nullptr) {
   float (&s_tile)[WAVES][kTpMaxFrames] = sm.tile;
   volatile uint32_t (&s_ev)[WAVES][64] = sm.ev;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -904,9 +910,15 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     const uint32_t got = s_ev[wave][lane];
     if (mine && (got & 0x10000u)) sampler_note(p, s0, got & 0xFFu, (got >> 8) & 1u);
   }
-  // frames of the block this lane's voice plays: a prefix, the index only moves forward
+  uint32_t lp_start = 0, lp_end = 0; // this lane's voice loops: its loop (end != 0) and s0.idx folded; otherwise 0, 0
+  if constexpr (LOOP) {
+    const SampleLoop lp = soa_load<SampleLoop>(loops, n, v);
+    if (mine && sampler_voice_loops(p, s0, lp)) { lp_start = lp.start; lp_end = lp.end; s0.idx = sample_loop_fold(s0.idx, lp.start, lp.end); }
+  }
+  // frames of the block this lane's voice plays: a prefix, the index only moves forward (a looping voice: the whole block)
   uint32_t valid = 0;
-  if (mine && s0.playing && frames) {
+  if (LOOP && lp_end) valid = frames;
+  else if (mine && s0.playing && frames) {
     const uint64_t lim = (uint64_t)p.length << 44;
     if (s0.idx < lim) {
       const uint64_t room = lim - s0.idx - 1; // idx + f * step <= lim - 1
@@ -932,6 +944,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     uint32_t off[U], len[U], playing[U];
     float gain[U];
     uint64_t idx[U], step[U];
+    uint32_t ls[LOOP ? U : 1], le[LOOP ? U : 1]; // a looping voice's loop; le == 0: the voice does not loop
     uint32_t any = 0;
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
@@ -942,6 +955,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
       idx[u] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)idx_hi, k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)idx_lo, k);
       step[u] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)step_hi, k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)step_lo, k);
       playing[u] = k0 + u < cnt ? (uint32_t)__builtin_amdgcn_readlane((int)s0.playing, k) : 0u;
+      if constexpr (LOOP) { ls[u] = (uint32_t)__builtin_amdgcn_readlane((int)lp_start, k); le[u] = (uint32_t)__builtin_amdgcn_readlane((int)lp_end, k); }
       any |= playing[u];
     }
     if (!any) continue; // (uniform)
@@ -955,13 +969,17 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
 #pragma unroll
       for (uint32_t j = 0; j < kTpChunk; ++j) {
         const uint32_t f = n0 + j;
-        const uint32_t i = (uint32_t)((idx[u] + (uint64_t)f * step[u]) >> 44);
+        uint64_t pos = idx[u] + (uint64_t)f * step[u];
+        if constexpr (LOOP) pos = sample_loop_pos(idx[u], (uint64_t)f * step[u], ls[u], le[u]);
+        const uint32_t i = (uint32_t)(pos >> 44);
         ok[u][j] = playing[u] && f < frames && i < len[u];
         if constexpr (INTERP) {
           const uint32_t ic = i < len[u] ? i : len[u] - 1;
 #pragma unroll
           for (int m = 0; m < Taps::N; ++m) {
-            const size_t at = (size_t)off[u] + sample_tap_clamped(ic, Taps::FIRST + m, len[u]);
+            size_t at = (size_t)off[u];
+            if constexpr (LOOP) at += sample_loop_tap_clamped(ic, Taps::FIRST + m, len[u], ls[u], le[u]);
+            else at += sample_tap_clamped(ic, Taps::FIRST + m, len[u]);
             if constexpr (STEREO) {
               const SamplePair t = reinterpret_cast<const SamplePair*>(bank)[at];
               tap[u][j][m] = t.l; tap_r[u][j][m] = t.r;
@@ -985,16 +1003,18 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
 #pragma unroll
       for (uint32_t j = 0; j < kTpChunk; ++j) {
         if constexpr (INTERP) { // the taps past either end of the sample dropped, then the mode's formula at this frame's fraction
-          const uint64_t pos = idx[u] + (uint64_t)(n0 + j) * step[u];
+          uint64_t pos = idx[u] + (uint64_t)(n0 + j) * step[u];
+          if constexpr (LOOP) pos = sample_loop_pos(idx[u], (uint64_t)(n0 + j) * step[u], ls[u], le[u]);
           const uint32_t i = (uint32_t)(pos >> 44);
           const float t = sample_fraction(pos);
+          const uint32_t lend = LOOP ? le[LOOP ? u : 0] : 0u; // (0: sample_tap_inside)
           float q[Taps::N];
 #pragma unroll
-          for (int m = 0; m < Taps::N; ++m) q[m] = sample_tap_inside(i, Taps::FIRST + m, len[u]) ? tap[u][j][m] : 0.0f;
+          for (int m = 0; m < Taps::N; ++m) q[m] = sample_loop_tap_inside(i, Taps::FIRST + m, len[u], lend) ? tap[u][j][m] : 0.0f;
           raw[u][j] = sample_interp<MODE>(q, t);
           if constexpr (STEREO) {
 #pragma unroll
-            for (int m = 0; m < Taps::N; ++m) q[m] = sample_tap_inside(i, Taps::FIRST + m, len[u]) ? tap_r[u][j][m] : 0.0f;
+            for (int m = 0; m < Taps::N; ++m) q[m] = sample_loop_tap_inside(i, Taps::FIRST + m, len[u], lend) ? tap_r[u][j][m] : 0.0f;
             raw_r[u][j] = sample_interp<MODE>(q, t);
           }
         }
@@ -1043,14 +1063,15 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
   if (mine && frames) {
     SamplerState s = s0;
     s.idx = s0.idx + (uint64_t)valid * s0.step;
+    if constexpr (LOOP) s.idx = sample_loop_pos(s0.idx, (uint64_t)valid * s0.step, lp_start, lp_end);
     if (s0.playing && valid < frames) s.playing = 0; // ran off the end inside the block
     soa_store(a.state, n, v, s);
   }
 }
-template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST>
-__global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw) {
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
+__global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw, const uint32_t* __restrict__ loops) {
   __shared__ SamplerTpSmem<kSamplerTpWaves, STEREO> sm;
-  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO, MODE>(a, bank, ie, vpw, tp_wg_own(), sm);
+  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO, MODE, LOOP>(a, bank, ie, vpw, tp_wg_own(), sm, loops);
 }
 // ------------------------------------------------------------------ several small banks in ONE launch (round 5)
 // A project of a few small banks of different kinds (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096
@@ -1096,7 +1117,7 @@ inline uint32_t mixed_sampler_workgroups(uint32_t n, uint32_t vpw) { const uint3
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done = nullptr); // welsh.vpw 1 | 2, fm.vpw 1 | 4
 void launch_welsh_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.bq_coef set (block-writing form): the BiQuad head fused; done: an event bound to the dispatch
 void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.vpw voices per wavefront (1, 2, 4)
-void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames; interpolation: a groove_sample_interpolation
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const uint32_t* loops, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames; interpolation: a groove_sample_interpolation; loops: the voices' SampleLoop words [2][n], null for a bank without a looped sample
 inline uint32_t welsh_tp_workgroups(uint32_t n, uint32_t vpw = 1) { return (n + kTpWaves * vpw - 1) / (kTpWaves * vpw); } // FM: groups of 4 vpw voices per workgroup, plain order
 inline uint32_t welsh_tp_grid(uint32_t n, uint32_t vpw = 1) { // Welsh: padded for the XCD-aware mapping (idle workgroups write zero rows)
   const uint32_t g = welsh_tp_workgroups(n, vpw);

@@ -404,6 +404,7 @@ class Sampler(Instrument):
         h = C.c_void_p()
         _lib.check(create(ctx.h, pcm.ctypes.data_as(_fp), pcm.shape[0], descs, len(descs), params, len(params), C.byref(h)), ctx.h)
         super().__init__(ctx, h, len(params))
+        self.n_samples = len(descs)
 
     @property
     def sample_channels(self):
@@ -419,6 +420,24 @@ class Sampler(Instrument):
     def sample_interpolation(self, mode):
         """groove_bank_set_sample_interpolation: from the next render on; parameters and state stay as they are."""
         _lib.check(self.ctx.L.groove_bank_set_sample_interpolation(self.h, mode), self.ctx.h)
+
+    @property
+    def sample_loops(self):
+        """groove_bank_sample_loops: one (start, end) per sample of the bank, in frames inside the sample; (0, 0): no loop."""
+        n = self.n_samples
+        out = (T.SampleLoop * n)()
+        self.ctx.L.groove_bank_sample_loops(self.h, out, n)
+        return [(l.start, l.end) for l in out]
+
+    @sample_loops.setter
+    def sample_loops(self, loops):
+        """groove_bank_set_sample_loops: one (start, end) per sample, or None to clear every loop; from the next render on, parameters
+        and state stay as they are."""
+        if loops is None:
+            _lib.check(self.ctx.L.groove_bank_set_sample_loops(self.h, None, 0), self.ctx.h)
+            return
+        arr = (T.SampleLoop * len(loops))(*[T.SampleLoop(int(s), int(e)) for s, e in loops])
+        _lib.check(self.ctx.L.groove_bank_set_sample_loops(self.h, arr, len(loops)), self.ctx.h)
 
 
 class Effect:

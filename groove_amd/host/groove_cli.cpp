@@ -1,7 +1,7 @@
 // groove-cli-hip — offline renderer, the GPU-path counterpart of the reference's `groove-cli`
 // (/root/reference/src/bin/groove-cli.rs:24-53 args, :56-158 main; gated at the reference commit).
 //
-//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--quiet] [--perf] [--debug] FILE...
+//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--quiet] [--perf] [--debug] FILE...
 //
 // --device-filter-links: `controls` onto a filter's cutoff, q or passband-ripple stay on the device (Orchestrator::set_filter_links_on_device),
 // a signal source's among them, which are dropped with a warning otherwise.
@@ -17,6 +17,8 @@
 // stereo file is the mean of its channels.
 // --sample-interpolation nearest|linear|cubic: how samplers and drumkits read their samples between frames
 // (Orchestrator::set_sample_interpolation); nearest, the reference's reading, by default.
+// --sample-loops: a sampler whose WAV file carries a forward sustain loop (`smpl` chunk) repeats it while a note is held
+// (Orchestrator::set_sample_loops); without it a sampler plays its file once.
 //
 // For each project file: SongSettings::new_from_project_file → instantiate → update_sample_rate(44100)
 // → run_performance(buffer) → (with --wav) send_performance_to_file(<input with .json5/.json → .wav>).
@@ -39,7 +41,7 @@ static std::string wav_name(const std::string& in) {
 }
 
 int main(int argc, char** argv) {
-  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false, instrument_controls = false, wet_links = false, wet_run = false, stereo_samples = false;
+  bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false, instrument_controls = false, wet_links = false, wet_run = false, stereo_samples = false, sample_loops = false;
   int device = 0;
   uint32_t sample_interpolation = GROOVE_SAMPLE_NEAREST;
   std::string assets = "assets";
@@ -57,6 +59,7 @@ int main(int argc, char** argv) {
     else if (a == "--device-wet-links") wet_links = true;
     else if (a == "--wet-reverb-run") wet_run = true;
     else if (a == "--stereo-samples") stereo_samples = true;
+    else if (a == "--sample-loops") sample_loops = true;
     else if (a == "--sample-interpolation" && i + 1 < argc) {
       const std::string m = argv[++i];
       if (m == "nearest") sample_interpolation = GROOVE_SAMPLE_NEAREST;
@@ -68,7 +71,7 @@ int main(int argc, char** argv) {
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--version" || a == "-v") { std::printf("groove-cli-hip 0.1 (MI355X render path)\n"); return 0; }
     else if (a == "--help" || a == "-h") {
-      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--quiet] [--perf] [--debug] FILE...\n");
+      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--quiet] [--perf] [--debug] FILE...\n");
       return 0;
     } else inputs.push_back(a);
   }
@@ -90,6 +93,7 @@ int main(int argc, char** argv) {
     o.set_instrument_controls_on_device(instrument_controls);
     o.set_wet_links_on_device(wet_links);
     o.set_stereo_samples(stereo_samples);
+    o.set_sample_loops(sample_loops);
     if (o.set_sample_interpolation(sample_interpolation)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (o.set_wet_reverb_run(wet_run)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (instantiate(o, desc, assets, synthetic)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }

@@ -852,6 +852,17 @@ void gh_set_wet_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_wet_l
 int gh_wet_links_on_device(void* h) { return ((Orchestrator*)h)->wet_links_on_device() ? 1 : 0; }
 void gh_set_stereo_samples(void* h, int on) { ((Orchestrator*)h)->set_stereo_samples(on != 0); }
 int gh_stereo_samples(void* h) { return ((Orchestrator*)h)->stereo_samples() ? 1 : 0; }
+void gh_set_sample_loops(void* h, int on) { ((Orchestrator*)h)->set_sample_loops(on != 0); }
+int gh_sample_loops(void* h) { return ((Orchestrator*)h)->sample_loops() ? 1 : 0; }
+// The forward loop [start, end) of the one sample of a sampler added by gh_add_sampler / gh_add_sampler_stereo (0, 0: none).
+int gh_set_sample_loop(void* h, int uid, uint32_t start, uint32_t end) {
+  Orchestrator* o = (Orchestrator*)h;
+  VoiceBankInstrument* e = uid >= 0 ? dynamic_cast<VoiceBankInstrument*>(o->get((Uid)uid)) : nullptr;
+  if (!e || e->bank_controls() != BankControls::SAMPLER) { o->fail("gh_set_sample_loop: not a sampler"); return 1; }
+  const groove_sample_loop loop{start, end};
+  if (groove_bank_set_sample_loops(e->bank(), &loop, 1)) { o->fail(groove_last_error(o->ctx())); return 1; }
+  return 0;
+}
 int gh_set_sample_interpolation(void* h, uint32_t mode) { return ((Orchestrator*)h)->set_sample_interpolation(mode); }
 uint32_t gh_sample_interpolation(void* h) { return ((Orchestrator*)h)->sample_interpolation(); }
 int gh_set_wet_reverb_run(void* h, int on) { return ((Orchestrator*)h)->set_wet_reverb_run(on != 0); }

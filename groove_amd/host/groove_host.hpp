@@ -490,6 +490,11 @@ class Orchestrator {
   // reference's reading.  An unknown mode is refused (last_error) and changes nothing.
   int set_sample_interpolation(uint32_t mode);
   uint32_t sample_interpolation() const { return sample_interpolation_; }
+  // A `sampler` a project's instantiation creates from here on takes the forward sustain loop its WAV file carries (project.hpp
+  // read_wav_loop; groove_bank_set_sample_loops): a held note then outlasts the file.  Drumkits never do: their voices are one-shots.
+  // Off by default: a sampler plays its file once, as the reference does.
+  void set_sample_loops(bool on) { sample_loops_ = on; }
+  bool sample_loops() const { return sample_loops_; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -537,6 +542,7 @@ class Orchestrator {
   bool wet_links_on_device_ = false;
   bool instrument_controls_on_device_ = false;
   bool stereo_samples_ = false;
+  bool sample_loops_ = false;
   uint32_t sample_interpolation_ = GROOVE_SAMPLE_NEAREST;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead

@@ -590,6 +590,46 @@ int read_wav_root_note(const std::string& path) {
   return smpl >= 0 ? smpl : acid;
 }
 
+bool read_wav_loop(const std::string& path, uint32_t* start, uint32_t* end, std::string* warning) {
+  if (start) *start = 0;
+  if (end) *end = 0;
+  WavData w;
+  if (!wav_open(path, w, nullptr)) return false;
+  const std::string& data = w.data;
+  size_t pos = 12;
+  while (pos + 8 <= data.size()) {
+    const std::string id = data.substr(pos, 4);
+    const size_t len = w.rd32(pos + 4);
+    if (id == "smpl") {
+      // smpl: nine words (.., number of loops at byte 28, sampler data at 32), then 24 bytes per loop: cue point, type, start, end, fraction, play count
+      const size_t avail = std::min(len, data.size() - (pos + 8));
+      if (avail < 36) { if (warning) *warning = "smpl chunk shorter than its header: " + path; return false; }
+      const uint32_t n_loops = w.rd32(pos + 8 + 28);
+      if (!n_loops) return false;
+      size_t rec = 0; // the first record of type 0 (forward) among the n_loops the header counts, each inside the chunk
+      uint32_t other = 0;
+      for (uint32_t r = 0; r < n_loops && !rec; ++r) {
+        if (avail < 36 + 24 * ((size_t)r + 1)) { if (warning) *warning = "smpl chunk ends before its loop record " + std::to_string(r) + ": " + path; return false; }
+        const uint32_t type = w.rd32(pos + 8 + 36 + 24 * (size_t)r + 4);
+        if (type == 0) rec = pos + 8 + 36 + 24 * (size_t)r;
+        else if (!other) other = type;
+      }
+      if (!rec) { if (warning) *warning = "smpl loop of type " + std::to_string(other) + " (only forward loops, type 0, are played): " + path; return false; }
+      const uint32_t first = w.rd32(rec + 8), last = w.rd32(rec + 12);
+      if (first > last || (size_t)last >= w.frames) {
+        if (warning) *warning = "smpl loop " + std::to_string(first) + " .. " + std::to_string(last) + " does not fit the file's " + std::to_string(w.frames) + " frames: " + path;
+        return false;
+      }
+      if (start) *start = first;
+      if (end) *end = last + 1;
+      return true;
+    }
+    if (len > data.size()) break;
+    pos += 8 + len + (len & 1);
+  }
+  return false;
+}
+
 namespace {
 // Drumkit "707": GM percussion key → sample file (Appendix A.10).
 const std::pair<int, const char*> k707[] = {
@@ -640,6 +680,7 @@ extern "C" int gh_add_welsh(void*, const groove_welsh_params*, uint32_t);
 extern "C" int gh_add_fm(void*, const groove_fm_params*, uint32_t);
 extern "C" int gh_add_sampler(void*, const float*, uint64_t, double, uint32_t);
 extern "C" int gh_add_toy_instrument(void*, double, double);
+extern "C" int gh_set_sample_loop(void*, int, uint32_t, uint32_t);
 #endif
 } // namespace
 
@@ -709,6 +750,12 @@ int instantiate(Orchestrator& o, const ProjectDesc& p, const std::string& assets
       if (!(root > 0.0)) { const int note = read_wav_root_note(path); root = note >= 0 ? note_to_frequency(note) : 440.0; }
       if (ch == 2) uid = gh_add_sampler_stereo(&o, pcm.data(), pcm.size() / 2, root, 8);
       else uid = gh_add_sampler(&o, pcm.data(), pcm.size(), root, 8);
+      if (uid >= 0 && o.sample_loops()) { // set_sample_loops: the file's forward sustain loop, if it carries one
+        uint32_t ls = 0, le = 0;
+        std::string warning;
+        if (read_wav_loop(path, &ls, &le, &warning)) { if (gh_set_sample_loop(&o, uid, ls, le)) return 1; }
+        else if (!warning.empty()) std::fprintf(stderr, "Warning: %s\n", warning.c_str());
+      }
     } else {
       return o.fail("instrument kind '" + d.kind + "' is not an instrument kind (settings/src/instruments.rs:26-39)");
     }
@@ -837,6 +884,8 @@ char* gh_project_describe_text(const char* text, const char* assets_root, char* 
 void gh_free(void* p) { std::free(p); }
 // The root note a WAV file carries (smpl chunk, else acid chunk), or -1.
 int gh_read_wav_root_note(const char* path) { return groove_host::read_wav_root_note(path ? path : ""); }
+// The forward loop a WAV file carries (read_wav_loop): 1 and [*start, *end), or 0.
+int gh_read_wav_loop(const char* path, uint32_t* start, uint32_t* end) { return groove_host::read_wav_loop(path ? path : "", start, end) ? 1 : 0; }
 // Welsh patch JSON text → groove_welsh_params (no GPU).
 int gh_welsh_params_from_patch_json(const char* text, groove_welsh_params* out, char* err, size_t err_len) {
   try {

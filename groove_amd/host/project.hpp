@@ -87,6 +87,12 @@ groove_welsh_params welsh_params_from_raw_json(const json5::Value& params, std::
 // The MIDI root note a WAV file carries: the `smpl` chunk's unity note, else the `acid` chunk's root note (when its flags say it is
 // set; test-data/samples/riff-acidized.wav: 57), else -1.
 int read_wav_root_note(const std::string& path);
+// The forward sustain loop a WAV file carries: the first loop record of type 0 (forward) of its `smpl` chunk — records of other types
+// before it are passed over — as frames [*start, *end) of the file (the record's dwEnd is the last frame played, so *end = dwEnd + 1).
+// Every record looked at has to lie inside the chunk, and the loop inside the file's frames; a file whose loops are all ping-pong or
+// reverse ones, whose chunk ends before a forward record is found, or whose forward loop does not fit gives false, 0, 0 and says why in
+// *warning (optional); a file without the chunk or without a loop gives false and no warning.
+bool read_wav_loop(const std::string& path, uint32_t* start, uint32_t* end, std::string* warning = nullptr);
 // Mono PCM from a WAV file (16/24/32-bit int or 32-bit float, any channel count: channels averaged).
 bool read_wav_mono(const std::string& path, std::vector<float>& out, uint32_t* sample_rate, std::string* err);
 // The same parser, keeping the channels of a two-channel file: *channels = 2 and `out` holds interleaved left, right, each the (float) of

@@ -28,6 +28,8 @@ def load():
         "gh_add_sampler": (i, [vp, _fp, C.c_uint64, d, u32]), "gh_add_sampler_stereo": (i, [vp, _fp, C.c_uint64, d, u32]),
         "gh_set_stereo_samples": (None, [vp, i]), "gh_stereo_samples": (i, [vp]),
         "gh_set_sample_interpolation": (i, [vp, u32]), "gh_sample_interpolation": (u32, [vp]),
+        "gh_set_sample_loops": (None, [vp, i]), "gh_sample_loops": (i, [vp]), "gh_set_sample_loop": (i, [vp, i, u32, u32]),
+        "gh_read_wav_loop": (i, [C.c_char_p, C.POINTER(u32), C.POINTER(u32)]),
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
         "gh_patch": (i, [vp, i, i]), "gh_patch_chain_to_main_mixer": (i, [vp, C.POINTER(C.c_int), u32]),
         "gh_unpatch_all": (None, [vp]), "gh_set_render_ahead": (None, [vp, i]), "gh_set_fused_direct": (None, [vp, i]), "gh_set_filter_links_on_device": (None, [vp, i]),
@@ -112,6 +114,17 @@ class Orchestrator:
             raise RuntimeError(self.L.gh_last_error(self.h).decode())
 
     def sample_interpolation(self): return self.L.gh_sample_interpolation(self.h)
+
+    def set_sample_loops(self, on):
+        """A `sampler` a project creates from here on takes the forward sustain loop its WAV file carries (off by default)."""
+        self.L.gh_set_sample_loops(self.h, int(bool(on)))
+
+    def sample_loops(self): return bool(self.L.gh_sample_loops(self.h))
+
+    def set_sample_loop(self, uid, start, end):
+        """The forward loop [start, end), in frames, of the sampler `uid` (add_sampler's return); 0, 0 clears it."""
+        if self.L.gh_set_sample_loop(self.h, uid, start, end):
+            raise RuntimeError(self.L.gh_last_error(self.h).decode())
 
     def add_effect(self, kind, params): return self.L.gh_add_effect(self.h, kind, C.byref(params))
     def patch(self, source, sink): return self.L.gh_patch(self.h, source, sink)

@@ -67,6 +67,8 @@ SYMBOLS = {
     "groove_bank_sample_channels": (_u32, [_vp]),
     "groove_bank_set_sample_interpolation": (_i, [_vp, _u32]),
     "groove_bank_sample_interpolation": (_u32, [_vp]),
+    "groove_bank_set_sample_loops": (_i, [_vp, C.POINTER(T.SampleLoop), _u32]),
+    "groove_bank_sample_loops": (_u32, [_vp, C.POINTER(T.SampleLoop), _u32]),
     "groove_bank_destroy": (_i, [_vp]),
     "groove_bank_voices": (_u32, [_vp]),
     "groove_bank_note_events": (_i, [_vp, C.POINTER(T.NoteEvent), _u32]),

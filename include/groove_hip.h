@@ -198,6 +198,22 @@ uint32_t groove_bank_sample_channels(groove_bank* bank);
  * GROOVE_SAMPLE_NEAREST for a bank of another kind. */
 int groove_bank_set_sample_interpolation(groove_bank* bank, uint32_t mode);
 uint32_t groove_bank_sample_interpolation(groove_bank* bank);
+/* FORWARD LOOPS: a held note outlasts the recording (docs/DSP_SPEC.md section 7).  loops[i] is the loop of the bank's i-th sample,
+ * n_samples the bank's sample count; loops == NULL clears every loop.  A voice loops while its sample has a loop, it is no one_shot
+ * voice (a drumkit voice ignores note-off and would never end) and it plays: its Q20.44 cursor is folded into [0, end) — F(x) = x
+ * below end << 44, start + (x - start) mod (end - start) from there on, exact 64-bit integers, for every length the create calls
+ * accept — so the end rule is never met and note-off stops it at the next block start as it stops any sampler voice (no release tail).
+ * The split of a render into blocks changes no bit of output or state.  Interpolation taps at or past `end` are read as the loop
+ * repeats, taps before the sample's first frame are silence; no tap of a looping voice lies outside [0, end).  Every other voice —
+ * on a sample without a loop, or a one_shot voice on a looped one — plays what it played before, bit for bit.  Like the interpolation
+ * mode a property of the bank: settable between any two renders (a cursor at or past `end` is folded at its next frame), kept by
+ * groove_bank_reset, a sample-rate change and groove_bank_set_param, touching neither parameters nor state.  The setter joins the
+ * bank's earlier work first, like groove_bank_set_param.  It is refused with a message for a bank of another kind, n_samples other
+ * than the bank's sample count, start >= end unless both are 0, and end beyond the sample's length.  groove_bank_kernel_form says
+ * ", looped" while a sample of the bank has a loop.  The getter writes the first min(cap, sample count) loops to `out` (NULL: none)
+ * and returns the number of looped samples; 0 for a bank of another kind. */
+int groove_bank_set_sample_loops(groove_bank* bank, const groove_sample_loop* loops, uint32_t n_samples);
+uint32_t groove_bank_sample_loops(groove_bank* bank, groove_sample_loop* out, uint32_t cap);
 int groove_bank_destroy(groove_bank* bank);
 uint32_t groove_bank_voices(groove_bank* bank);
 /* HandlesMidi::handle_midi_message → PlaysNotes::note_on/note_off (orchestrator.rs:737-739;
@@ -274,9 +290,9 @@ int groove_bank_render_mix_deferred(groove_bank* bank, uint32_t frames, float* b
  * deferred exactly as above (carried by the next such call, or flushed).  For projects with at most one time-parallel bank of each
  * kind and at most 2,048 partial rows in all (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096 sampler
  * voices, three launches whose durations added -> one); anything else is rendered bank by bank by groove_bank_render_mix_deferred in
- * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them, or one whose sample
- * interpolation is not GROOVE_SAMPLE_NEAREST, always takes that bank-by-bank path (the one launch's sampler body is the mono,
- * nearest one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
+ * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them, one whose sample
+ * interpolation is not GROOVE_SAMPLE_NEAREST, or one with a looped sample always takes that bank-by-bank path (the one launch's
+ * sampler body is the mono, nearest, loop-free one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
  * the same bits (one reduction over all rows instead of one per bank).  No reference counterpart as a call: the reference ticks
  * every instrument inside gather_audio. */
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate);

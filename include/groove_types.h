@@ -204,6 +204,10 @@ typedef enum {
   GROOVE_SAMPLE_CUBIC = 2    /* four taps, Catmull-Rom                                                              */
 } groove_sample_interpolation;
 
+/* One forward loop of a sample (groove_bank_set_sample_loops; docs/DSP_SPEC.md section 7): frames inside the sample, [start, end),
+ * 0 <= start < end <= length; 0, 0: none. */
+typedef struct { uint32_t start, end; } groove_sample_loop;
+
 /* Controller devices (the schema's third device class, settings/src/controllers.rs: "lfo", "signal-passthrough-controller")
  * as the SOURCE of a control link, groove_ctl_link_create.  docs/DSP_SPEC.md section 13 defines the value laws. */
 typedef enum {
