@@ -97,29 +97,62 @@ GROOVE_HD double ctl_trip_value(uint32_t kind, double start, double end, double 
   return start + rise;
 }
 
+// ------------------------------------------------------------------ routes
+// THE routing rule (include/groove_hip.h, groove_ctl_*_create): which parameter of which kind of target a link reaches, and as what.
+//   FLOAT, UINT  the device form IS the value: the float word (ceiling, attenuation, threshold: d_fa) or the uint word (bits: d_ua) the
+//                effect kernels read (groove_ctl_link_create, groove_ctl_trip_create)
+//   DERIVED      cutoff, q, passband-ripple: the link's kernel turns the value into the parameter by groove_fx_set_param's law and derives
+//                the lane's coefficients on the device (fx_coef.h) (groove_ctl_filter_link_create, groove_ctl_trip_create)
+//   WET          wet-dry-mix: the value itself into d_wet; the one host decision that hangs on it, a reverb's form, is made from the
+//                reverb's count of live wet links (groove_ctl_wet_link_create, groove_ctl_wet_trip_create)
+//   BANK         a word of a bank's voice records (groove_ctl_bank_link_create, groove_ctl_bank_trip_create)
+// ctl_fx_class is the class of a control index whatever the effect, ctl_fx_route the class where the kind has that parameter: the
+// library's creates, the host layer's orchestrator and the CPU tests all ask these two and ctl_bank_route.
+enum CtlRoute : uint32_t { CTL_ROUTE_NONE = 0, CTL_ROUTE_FLOAT, CTL_ROUTE_UINT, CTL_ROUTE_DERIVED, CTL_ROUTE_WET, CTL_ROUTE_BANK };
+enum BankKind { BANK_WELSH = 0, BANK_FM = 1, BANK_SAMPLER = 2 };
+GROOVE_HD CtlRoute ctl_fx_class(uint32_t control_index) {
+  switch (control_index) {
+    case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD: return CTL_ROUTE_FLOAT;
+    case GROOVE_CTL_FX_BITS: return CTL_ROUTE_UINT;
+    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE: return CTL_ROUTE_DERIVED;
+    case GROOVE_CTL_FX_WET: return CTL_ROUTE_WET;
+    default: return CTL_ROUTE_NONE;
+  }
+}
+GROOVE_HD CtlRoute ctl_fx_route(uint32_t fx_kind, uint32_t control_index) {
+  bool has = false; // does the kind's kernel read the parameter?  (the arrays are shared between kinds: groove_fx d_fa)
+  switch (control_index) {
+    case GROOVE_CTL_FX_CEILING: has = fx_kind == GROOVE_FX_GAIN; break;
+    case GROOVE_CTL_FX_BITS: has = fx_kind == GROOVE_FX_BITCRUSHER; break;
+    case GROOVE_CTL_FX_ATTENUATION: has = fx_kind == GROOVE_FX_REVERB; break;
+    case GROOVE_CTL_FX_THRESHOLD: has = fx_kind == GROOVE_FX_COMPRESSOR || fx_kind == GROOVE_FX_LIMITER; break;
+    case GROOVE_CTL_FX_CUTOFF: has = fx_kind_is_filter(fx_kind); break; // every IIR kind
+    case GROOVE_CTL_FX_Q: has = fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || fx_kind == GROOVE_FX_BIQUAD_AP12; break; // the formulas that read it
+    case GROOVE_CTL_FX_PASSBAND_RIPPLE: has = fx_kind == GROOVE_FX_BIQUAD_LP24; break;
+    case GROOVE_CTL_FX_WET: has = fx_kind != GROOVE_FX_MIXER; break; // a Mixer is the identity and launches nothing
+    default: break;
+  }
+  return has ? ctl_fx_class(control_index) : CTL_ROUTE_NONE;
+}
+// A Welsh bank's dca-gain, dca-pan and filter-cutoff; an FM bank's dca-gain, dca-pan, depth and beta; a sampler (drumkit) bank's gain.
+GROOVE_HD CtlRoute ctl_bank_route(uint32_t bank_kind, uint32_t control_index) {
+  bool has = false;
+  switch (bank_kind) {
+    case BANK_WELSH: has = control_index >= GROOVE_CTL_WELSH_DCA_GAIN && control_index <= GROOVE_CTL_WELSH_CUTOFF; break;
+    case BANK_FM: has = control_index >= GROOVE_CTL_FM_DCA_GAIN && control_index <= GROOVE_CTL_FM_BETA; break;
+    case BANK_SAMPLER: has = control_index == GROOVE_CTL_SAMPLER_GAIN; break;
+    default: break;
+  }
+  return has ? CTL_ROUTE_BANK : CTL_ROUTE_NONE;
+}
+
 // ------------------------------------------------------------------ targets
-// groove_fx_set_param's laws where the device form IS the value.  The others are derived on the host in f64 (cutoff, q,
-// passband-ripple -> coefficients; a FILTER link derives them on the device instead, below) or choose a kernel path there
-// (wet-dry-mix -> all_wet): a plain link cannot reach them.  wet-dry-mix has creates of its own (groove_ctl_wet_link_create /
-// groove_ctl_wet_trip_create): its device form is the value too (ctl_target_float / ctl_target_float_f64 below), and the one host
-// decision that hangs on it, a reverb's form, is made from the reverb's count of live wet links.
+// groove_fx_set_param's laws for the routes above, in the precision they have there.  (The predicates are the routes, asked the way the
+// CPU tests' shims ask.)
 GROOVE_HD bool ctl_target_linkable(uint32_t control_index) {
-  switch (control_index) {
-    case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_BITS: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD: return true;
-    default: return false;
-  }
+  return ctl_fx_class(control_index) == CTL_ROUTE_FLOAT || ctl_fx_class(control_index) == CTL_ROUTE_UINT;
 }
-// The parameters a FILTER link (groove_ctl_filter_link_create) reaches: the link's kernel turns the value into the parameter by
-// groove_fx_set_param's law and derives the lane's coefficients on the device (fx_coef.h).  cutoff: every IIR kind; q: the kinds whose
-// formula reads it; passband-ripple: the 24 dB low-pass.
-GROOVE_HD bool ctl_target_derived(uint32_t kind, uint32_t control_index) {
-  switch (control_index) {
-    case GROOVE_CTL_FX_CUTOFF: return fx_kind_is_filter(kind);
-    case GROOVE_CTL_FX_Q: return kind == GROOVE_FX_BIQUAD_LP12 || kind == GROOVE_FX_BIQUAD_HP12 || kind == GROOVE_FX_BIQUAD_AP12;
-    case GROOVE_CTL_FX_PASSBAND_RIPPLE: return kind == GROOVE_FX_BIQUAD_LP24;
-    default: return false;
-  }
-}
+GROOVE_HD bool ctl_target_derived(uint32_t kind, uint32_t control_index) { return ctl_fx_route(kind, control_index) == CTL_ROUTE_DERIVED; }
 // A filter lane's parameter shadow on the device, [word][lane]: what deriving its coefficients reads (groove_fx: d_shadow).
 enum : uint32_t { CTL_SHADOW_CUTOFF = 0, CTL_SHADOW_Q = 1, CTL_SHADOW_RIPPLE = 2, CTL_SHADOW_BANDWIDTH = 3, CTL_SHADOW_DB_GAIN = 4, CTL_SHADOW_WORDS = 5 };
 GROOVE_HD uint32_t ctl_shadow_word(uint32_t control_index) {
@@ -131,7 +164,7 @@ GROOVE_HD float ctl_derived_param_f64(uint32_t control_index, double value01) {
   return control_index == GROOVE_CTL_FX_CUTOFF ? (float)fx_percent_to_frequency(v) : (float)fx_q_law(v);
 }
 GROOVE_HD float ctl_derived_param(uint32_t control_index, float value01) { return ctl_derived_param_f64(control_index, (double)value01); }
-GROOVE_HD bool ctl_target_is_uint(uint32_t control_index) { return control_index == GROOVE_CTL_FX_BITS; }
+GROOVE_HD bool ctl_target_is_uint(uint32_t control_index) { return ctl_fx_class(control_index) == CTL_ROUTE_UINT; }
 GROOVE_HD float ctl_target_float(float value01) { return value01; } // ceiling, threshold, attenuation
 GROOVE_HD uint32_t ctl_target_bits(float value01) {
   const uint32_t b = (uint32_t)(value01 * 16.0f);
@@ -149,9 +182,7 @@ GROOVE_HD uint32_t ctl_target_bits_f64(double value) {
 // ------------------------------------------------------------------ targets on a Welsh bank
 // A BANK link (groove_ctl_bank_link_create / groove_ctl_bank_trip_create) reaches the three controls groove_bank_set_param has, by that
 // call's own laws in the precision they have there: the float groove_welsh_params would hold.
-GROOVE_HD bool ctl_bank_target_ok(uint32_t control_index) {
-  return control_index == GROOVE_CTL_WELSH_DCA_GAIN || control_index == GROOVE_CTL_WELSH_DCA_PAN || control_index == GROOVE_CTL_WELSH_CUTOFF;
-}
+GROOVE_HD bool ctl_bank_target_ok(uint32_t control_index) { return ctl_bank_route(BANK_WELSH, control_index) != CTL_ROUTE_NONE; }
 GROOVE_HD float ctl_bank_gain_f64(double value) { return (float)clamp01d(value); }
 GROOVE_HD float ctl_bank_pan_f64(double value) { // ControlValue 0..1 -> BipolarNormal
   GROOVE_NO_CONTRACT
@@ -179,8 +210,8 @@ enum : uint32_t { CTL_DCA_GAIN = 0, CTL_DCA_PAN = 1, CTL_DCA_WORDS = 2 };
 // groove_bank_set_param's laws for those kinds: the float groove_fm_params / groove_sampler_params would hold.  gain and pan are the
 // Welsh laws above; depth is a Normal and beta a plain ParameterType set from the ControlValue as it is — (float)clamp01(v) both (spec
 // decisions, docs/DSP_SPEC.md section 13); `ratio` has no law anywhere and no control.
-GROOVE_HD bool ctl_fm_target_ok(uint32_t control_index) { return control_index >= GROOVE_CTL_FM_DCA_GAIN && control_index <= GROOVE_CTL_FM_BETA; }
-GROOVE_HD bool ctl_sampler_target_ok(uint32_t control_index) { return control_index == GROOVE_CTL_SAMPLER_GAIN; }
+GROOVE_HD bool ctl_fm_target_ok(uint32_t control_index) { return ctl_bank_route(BANK_FM, control_index) != CTL_ROUTE_NONE; }
+GROOVE_HD bool ctl_sampler_target_ok(uint32_t control_index) { return ctl_bank_route(BANK_SAMPLER, control_index) != CTL_ROUTE_NONE; }
 GROOVE_HD float ctl_fm_depth_f64(double value) { return (float)clamp01d(value); }
 GROOVE_HD float ctl_fm_beta_f64(double value) { return (float)clamp01d(value); }
 GROOVE_HD float ctl_sampler_gain_f64(double value) { return (float)clamp01d(value); }
@@ -227,6 +258,23 @@ GROOVE_HD void ctl_fm_store(uint32_t* params, float* shadow, uint32_t n_voices, 
 // ... and onto voice e of a sampler bank: its gain is one word of the record.
 GROOVE_HD void ctl_sampler_store(uint32_t* params, uint32_t n_voices, uint32_t e, float mine) {
   params[(size_t)(offsetof(SamplerParams, gain) / 4) * n_voices + e] = __builtin_bit_cast(uint32_t, mine);
+}
+
+// ------------------------------------------------------------------ the two device buffers of a link's source
+// Byte offsets of the sections, 64-bit words first and the uint32 tail last; `bytes` is the allocation.  The host fills a staging copy
+// through these and the kernels' views (ctl_link.h: CtlLanes, CtlTrip) are carved out by them: the one statement of each layout.
+// An LFO / signal link: delta64[n_src], duty64[n_src] as uint64, then waveform[n_src], law[n_src] as uint32.
+struct CtlLanesLayout { size_t delta64, duty64, waveform, law, bytes; };
+GROOVE_HD CtlLanesLayout ctl_lanes_layout(uint32_t n_src) {
+  const size_t n = n_src;
+  return {0, 8 * n, 16 * n, 20 * n, 24 * n};
+}
+// A trip link, SoA [step][source lane]: begin[n_steps + 1][n_src], start, end, beats [n_steps][n_src] as f64, then kind[n_steps][n_src]
+// as uint32, padded to a whole 64-bit word.
+struct CtlTripLayout { size_t begin, start, end, beats, kind, bytes; };
+GROOVE_HD CtlTripLayout ctl_trip_layout(uint32_t n_src, uint32_t n_steps) {
+  const size_t rows = (size_t)n_steps * n_src, start = 8 * (rows + n_src);
+  return {0, start, start + 8 * rows, start + 16 * rows, start + 24 * rows, start + 24 * rows + 8 * ((rows + 1) / 2)};
 }
 
 } // namespace groove

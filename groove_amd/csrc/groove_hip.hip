@@ -79,8 +79,7 @@ struct groove_block {
   bool sums_on_ap = false; // the valid lane sums are d_sums_ap[ap_flip], written on the all-pass stream
 };
 
-enum BankKind { BANK_WELSH = 0, BANK_FM = 1, BANK_SAMPLER = 2 };
-
+// (BankKind — BANK_WELSH, BANK_FM, BANK_SAMPLER — is ctl_core.h's: the control links' route table is asked by it)
 
 // One distinct filter description of a Welsh patch: what derive.h welsh_filter_f32_error depends on (welsh_upload_params).
 struct F32FilterKey {
@@ -185,22 +184,22 @@ struct groove_fx {
   bool done_recorded = true;    // false: the last use was a kernel whose end another event marks (a fused render's): ev_done is recorded on demand
 };
 
-// A controller linked to one parameter of an effect (groove_ctl_link_*; csrc/ctl_link.h).  Everything the apply kernel reads
-// lives on the device: the per-source-lane description (uploaded once, and again when the sample rate changes), the captured
-// samples and the flag that says there are any.
+// A controller linked to one parameter of one target (groove_ctl_*; csrc/ctl_link.h).  The target is one of four, by the route of
+// (target kind, control_index) (ctl_core.h: ctl_fx_route, ctl_bank_route): an effect's plain parameter words (d_fa, d_ua, or d_wet for a
+// wet link), a filter's parameter shadow and coefficients, a Welsh bank's records, an FM or sampler bank's voices.  Everything the apply
+// kernel reads of the SOURCE lives on the device: an LFO's or signal's per-source-lane description (uploaded once, and again when the
+// sample rate changes), the captured samples and the flag that says there are any; or a trip's step table.
 struct groove_ctl_link {
   groove_ctx* ctx;
   uint32_t source, n_src, control_index;
   groove_fx* target; // nullptr once the target has been destroyed (groove_fx_destroy clears it), and on a bank link
   groove_bank* bank = nullptr; // a bank link's target (groove_ctl_bank_link_create); on_bank stays set when groove_bank_destroy clears it
   bool on_bank = false;
-  bool derived = false; // a filter link (groove_ctl_filter_link_create): the apply derives the target lanes' coefficients
   std::vector<groove_ctl_source> src;
-  uint64_t* d_lanes = nullptr; // delta64[n_src], duty64[n_src], then waveform[n_src], law[n_src] as uint32
+  uint64_t* d_lanes = nullptr; // the LFO / signal lanes (ctl_core.h: ctl_lanes_layout)
   float* d_value = nullptr;    // [n_src] captured samples (signal source)
   uint32_t* d_captured = nullptr;
-  // a trip link (groove_ctl_trip_create): begin[n_steps + 1][n_src], start, end, beats [n_steps][n_src] as f64, then kind[n_steps][n_src]
-  // as uint32 — uploaded once: nothing in it depends on the sample rate
+  // a trip link's step table (ctl_core.h: ctl_trip_layout) — uploaded once: nothing in it depends on the sample rate
   double* d_trip = nullptr;
   uint32_t n_steps = 0;
 };
@@ -1064,21 +1063,34 @@ int fx_check_uniform(groove_fx* fx) {
 }
 
 // ---- control links ----------------------------------------------------------------------
+// The sections of a link's two source buffers, on the device or in a host staging copy: ctl_core.h's layouts are the only offsets.
+template <typename T> T* ctl_section(void* base, size_t byte_offset) { return reinterpret_cast<T*>(static_cast<char*>(base) + byte_offset); }
+CtlLanes ctl_lanes_view(const groove_ctl_link* l) {
+  const CtlLanesLayout at = ctl_lanes_layout(l->n_src);
+  return {ctl_section<uint64_t>(l->d_lanes, at.delta64), ctl_section<uint64_t>(l->d_lanes, at.duty64), ctl_section<uint32_t>(l->d_lanes, at.waveform),
+          ctl_section<uint32_t>(l->d_lanes, at.law)};
+}
+CtlTrip ctl_trip_view(const groove_ctl_link* l) {
+  const CtlTripLayout at = ctl_trip_layout(l->n_src, l->n_steps);
+  return {ctl_section<double>(l->d_trip, at.begin), ctl_section<double>(l->d_trip, at.start), ctl_section<double>(l->d_trip, at.end),
+          ctl_section<double>(l->d_trip, at.beats), ctl_section<uint32_t>(l->d_trip, at.kind), l->n_steps};
+}
 // The device copy of a link's source lanes at the current sample rate (creation, groove_update_sample_rate: the caller has
 // waited for the ctx stream, or nothing has used the buffer yet).
 int ctl_upload_lanes(groove_ctl_link* l) {
   groove_ctx* ctx = l->ctx;
-  const uint32_t n = l->n_src;
-  std::vector<uint64_t> w((size_t)3 * n);
-  uint32_t* u = reinterpret_cast<uint32_t*>(w.data() + (size_t)2 * n);
-  for (uint32_t i = 0; i < n; ++i) {
+  const CtlLanesLayout at = ctl_lanes_layout(l->n_src);
+  std::vector<uint64_t> w(at.bytes / 8);
+  uint64_t *delta64 = ctl_section<uint64_t>(w.data(), at.delta64), *duty64 = ctl_section<uint64_t>(w.data(), at.duty64);
+  uint32_t *waveform = ctl_section<uint32_t>(w.data(), at.waveform), *law = ctl_section<uint32_t>(w.data(), at.law);
+  for (uint32_t i = 0; i < l->n_src; ++i) {
     const groove_ctl_source& s = l->src[i];
-    w[i] = ctl_lfo_delta64(s.frequency_hz, (double)ctx->sr);
-    w[n + i] = ctl_lfo_duty64(s.waveform, s.duty);
-    u[i] = s.waveform;
-    u[n + i] = s.law;
+    delta64[i] = ctl_lfo_delta64(s.frequency_hz, (double)ctx->sr);
+    duty64[i] = ctl_lfo_duty64(s.waveform, s.duty);
+    waveform[i] = s.waveform;
+    law[i] = s.law;
   }
-  GHIP(ctx, ctx_memcpy(ctx, l->d_lanes, w.data(), w.size() * 8, hipMemcpyHostToDevice));
+  GHIP(ctx, ctx_memcpy(ctx, l->d_lanes, w.data(), at.bytes, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -2930,300 +2942,46 @@ int groove_fx_set_param(groove_fx* fx, uint32_t lane, uint32_t control_index, do
 }
 
 // ============================================================================ control links
-// What both kinds of link ask of their arguments and sources, and the link itself once the target has been accepted.
-static int bank_link_apply(groove_ctl_link* l, const char* who, uint64_t at); // (links onto a Welsh bank: below, with their creates)
-static int ctl_link_check(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
+// Six creates, two sources times the effect / wet / bank entry points, are thin: each owns its `who` and the sentences it refuses with;
+// what they share is below, in the order a create uses it.  The route table (ctl_core.h: ctl_fx_class, ctl_fx_route, ctl_bank_route)
+// says which class a parameter is in.
+// What every create onto an effect asks of its arguments (have_source: the source's own pointers are there) and its target.
+static int fx_link_check(groove_ctx* ctx, const char* who, bool have_source, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
   const std::string w = std::string(who) + ": ";
-  if (!ctx || !src || !target || !out) return fail(ctx, w + "NULL argument");
+  if (!ctx || !have_source || !target || !out) return fail(ctx, w + "NULL argument");
   if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, w + "the target is not a live effect of this context");
   if (n_src != 1 && n_src != target->n) return fail(ctx, w + "n_src must be the target's lane count, or 1 (broadcast)");
   return 0;
 }
-static int ctl_link_check_sources(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src) {
-  const std::string w = std::string(who) + ": ";
-  for (uint32_t i = 0; i < n_src; ++i) {
-    if (src[i].source != GROOVE_CTL_SRC_LFO && src[i].source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, w + "unknown source kind");
-    if (src[i].source != src[0].source) return fail(ctx, w + "the lanes of one link share one source kind");
-    if (src[i].source == GROOVE_CTL_SRC_LFO) {
-      if (!ctl_lfo_waveform_ok(src[i].waveform))
-        return fail(ctx, w + "an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine (a noise generator's state at a block start has no closed form)");
-      if (!(src[i].frequency_hz >= 0.0) || !(src[i].frequency_hz < (double)ctx->sr)) return fail(ctx, w + "LFO frequency outside [0, sample rate)");
-    } else if (!ctl_signal_law_ok(src[i].law)) {
-      return fail(ctx, w + "unknown signal law");
-    }
-  }
-  return 0;
-}
-static int ctl_link_make(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
-                         bool derived, groove_ctl_link** out) {
-  const std::string w = std::string(who) + ": ";
-  GHIP(ctx, hipSetDevice(ctx->device));
-  groove_ctl_link* l = new groove_ctl_link();
-  l->ctx = ctx; l->source = src[0].source; l->n_src = n_src; l->control_index = control_index; l->target = target; l->derived = derived;
-  l->src.assign(src, src + n_src);
-  if (hipMalloc(&l->d_lanes, (size_t)3 * n_src * 8) != hipSuccess || hipMalloc(&l->d_value, (size_t)n_src * 4) != hipSuccess ||
-      hipMalloc(&l->d_captured, 4) != hipSuccess) {
-    groove_ctl_link_destroy(l);
-    return fail(ctx, w + "hipMalloc failed");
-  }
-  if (hipMemsetAsync(l->d_value, 0, (size_t)n_src * 4, ctx->stream) != hipSuccess || hipMemsetAsync(l->d_captured, 0, 4, ctx->stream) != hipSuccess) {
-    groove_ctl_link_destroy(l);
-    return fail(ctx, w + "hipMemsetAsync failed");
-  }
-  if (ctl_upload_lanes(l)) { groove_ctl_link_destroy(l); return 1; } // (its message stands)
-  ctx->links.push_back(l);
-  *out = l;
-  return 0;
-}
-int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
-                           groove_ctl_link** out) {
-  const char* who = "groove_ctl_link_create";
-  if (ctl_link_check(ctx, who, src, n_src, target, out)) return 1;
-  switch (control_index) {
-    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE:
-      return fail(ctx, "groove_ctl_link_create: cutoff, q and passband-ripple become filter coefficients on the host (f64): not linkable on the device; use groove_fx_set_param");
-    case GROOVE_CTL_FX_WET:
-      return fail(ctx, "groove_ctl_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
-    default:
-      if (!ctl_target_linkable(control_index)) return fail(ctx, "groove_ctl_link_create: unknown control index");
-  }
-  // the parameter has to be one the target's kernels read: the arrays are shared between kinds (groove_fx: d_fa)
-  const bool fits = (control_index == GROOVE_CTL_FX_CEILING && target->kind == GROOVE_FX_GAIN) ||
-                    (control_index == GROOVE_CTL_FX_BITS && target->kind == GROOVE_FX_BITCRUSHER) ||
-                    (control_index == GROOVE_CTL_FX_ATTENUATION && target->kind == GROOVE_FX_REVERB) ||
-                    (control_index == GROOVE_CTL_FX_THRESHOLD && (target->kind == GROOVE_FX_COMPRESSOR || target->kind == GROOVE_FX_LIMITER));
-  if (!fits) return fail(ctx, "groove_ctl_link_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
-  if (ctl_link_check_sources(ctx, who, src, n_src)) return 1;
-  return ctl_link_make(ctx, who, src, n_src, target, control_index, false, out);
-}
-int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
-                                  groove_ctl_link** out) {
-  const char* who = "groove_ctl_filter_link_create";
-  if (ctl_link_check(ctx, who, src, n_src, target, out)) return 1;
-  switch (control_index) {
-    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE: break;
-    case GROOVE_CTL_FX_WET:
-      return fail(ctx, "groove_ctl_filter_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
-    case GROOVE_CTL_FX_CEILING: case GROOVE_CTL_FX_BITS: case GROOVE_CTL_FX_ATTENUATION: case GROOVE_CTL_FX_THRESHOLD:
-      return fail(ctx, "groove_ctl_filter_link_create: a filter link reaches cutoff, q or passband-ripple; this parameter's device form is the value itself: use groove_ctl_link_create");
-    default:
-      return fail(ctx, "groove_ctl_filter_link_create: unknown control index (a filter link reaches cutoff, q or passband-ripple)");
-  }
-  if (!ctl_target_derived(target->kind, control_index))
-    return fail(ctx, "groove_ctl_filter_link_create: the target's kind does not derive its coefficients from that parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)");
-  if (ctl_link_check_sources(ctx, who, src, n_src)) return 1;
-  GHIP(ctx, hipSetDevice(ctx->device));
-  if (!target->d_shadow) { // the first filter link onto this effect: from here on fx_upload_params keeps the shadow beside the coefficients
-    if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
-      target->d_shadow = nullptr;
-      return fail(ctx, "groove_ctl_filter_link_create: hipMalloc failed");
-    }
-    if (fx_acquire_ctx(target) || fx_upload_shadow(target)) return 1;
-  }
-  return ctl_link_make(ctx, who, src, n_src, target, control_index, true, out);
-}
-// ---- links onto wet-dry-mix
 // Every effect kernel reads d_wet[lane] at launch and takes `wm < 1` per lane; the one HOST decision that hangs on the value is a
 // reverb's form, and a reverb counts its live wet links for that (fx_needs_dry).  The law is groove_fx_set_param's (float)clamp01(v):
-// ctl_target_float / ctl_target_float_f64, which the existing apply kernels store — into d_wet instead of d_fa (ctl_float_words).
-// The applies' fx_ap_settle orders the store behind a direct all-pass kernel that is still reading d_wet on the all-pass stream
-// (events between streams: no host wait).
-static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src);
-static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
-                         uint32_t control_index, groove_ctl_link** out);
+// ctl_target_float / ctl_target_float_f64, stored into d_wet instead of d_fa.  The applies' fx_ap_settle orders the store behind a
+// direct all-pass kernel that is still reading d_wet on the all-pass stream (events between streams: no host wait).
 static int wet_link_check_target(groove_ctx* ctx, const char* who, groove_fx* target) {
-  if (target->kind == GROOVE_FX_MIXER) return fail(ctx, std::string(who) + ": a Mixer is the identity and launches nothing: it reads no wet-dry-mix");
+  if (!ctl_fx_route(target->kind, GROOVE_CTL_FX_WET)) return fail(ctx, std::string(who) + ": a Mixer is the identity and launches nothing: it reads no wet-dry-mix");
   return 0;
 }
-int groove_ctl_wet_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
-  const char* who = "groove_ctl_wet_link_create";
-  if (ctl_link_check(ctx, who, src, n_src, target, out) || wet_link_check_target(ctx, who, target) || ctl_link_check_sources(ctx, who, src, n_src)) return 1;
-  if (ctl_link_make(ctx, who, src, n_src, target, GROOVE_CTL_FX_WET, false, out)) return 1;
-  ++target->wet_links;
-  return 0;
-}
-int groove_ctl_wet_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src, groove_fx* target,
-                               groove_ctl_link** out) {
-  const char* who = "groove_ctl_wet_trip_create";
-  if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
-  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, std::string(who) + ": the target is not a live effect of this context");
-  if (n_src != 1 && n_src != target->n) return fail(ctx, std::string(who) + ": n_src must be the target's lane count, or 1 (broadcast)");
-  if (wet_link_check_target(ctx, who, target) || ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src)) return 1;
+// The first filter link onto this effect: from here on fx_upload_params keeps the parameter shadow beside the coefficients.
+static int fx_ensure_shadow(groove_fx* target, const char* who) {
+  groove_ctx* ctx = target->ctx;
   GHIP(ctx, hipSetDevice(ctx->device));
-  groove_ctl_link* l = nullptr;
-  if (ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, GROOVE_CTL_FX_WET, &l)) return 1;
-  l->target = target;
-  ++target->wet_links;
-  ctx->links.push_back(l);
-  *out = l;
-  return 0;
-}
-int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t frames) {
-  if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
-  groove_ctx* ctx = l->ctx;
-  if (blk->ctx != ctx) return fail(ctx, "groove_ctl_link_capture: link and block belong to different contexts");
-  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_capture: a trip link captures nothing (groove_ctl_trip_apply is its only call)");
-  if (l->source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_capture: not a signal link");
-  if (blk->n != l->n_src) return fail(ctx, "groove_ctl_link_capture: block lanes != source lanes");
-  if (frames > blk->cap) return fail(ctx, "groove_ctl_link_capture: frames > block capacity");
-  if (frames == 0) return 0; // nothing has been transformed
-  GHIP(ctx, hipSetDevice(ctx->device));
-  if (block_acquire(blk) || block_normalise(blk)) return 1; // the source lanes are in the caller's order, like an effect's
-  hipLaunchKernelGGL(ctl_capture_kernel, dim3(blocks_for(blk->n)), dim3(kThreads), 0, ctx->stream, blk->d, (size_t)blk->cap * blk->n, blk->n, frames - 1,
-                     l->d_value, l->d_captured);
-  GHIP(ctx, hipGetLastError());
-  return 0;
-}
-// The float words a plain effect link writes: the wet-dry mix for a wet link, parameter A otherwise.
-static float* ctl_float_words(const groove_ctl_link* l, groove_fx* fx) { return l->control_index == GROOVE_CTL_FX_WET ? fx->d_wet : fx->d_fa; }
-int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
-  if (!l) return fail(nullptr, "groove_ctl_link_apply: link is NULL");
-  groove_ctx* ctx = l->ctx;
-  groove_fx* fx = l->target;
-  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_apply: a trip link is applied at a musical time: use groove_ctl_trip_apply");
-  if (l->on_bank) return bank_link_apply(l, "groove_ctl_link_apply", at_frame);
-  if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_link_apply: the target effect has been destroyed");
-  GHIP(ctx, hipSetDevice(ctx->device));
-  if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
-  const uint32_t n = l->n_src;
-  const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + (size_t)2 * n);
-  const CtlLanes lanes{l->d_lanes, l->d_lanes + n, u, u + n};
-  if (l->derived) {
-    hipLaunchKernelGGL(ctl_filter_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
-                       fx->kind, l->control_index, (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n);
-    GHIP(ctx, hipGetLastError());
-    return 0;
+  if (target->d_shadow) return 0;
+  if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
+    target->d_shadow = nullptr;
+    return fail(ctx, std::string(who) + ": hipMalloc failed");
   }
-  const bool as_uint = ctl_target_is_uint(l->control_index);
-  hipLaunchKernelGGL(ctl_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, l->source, lanes, n, at_frame, l->d_value, l->d_captured,
-                     as_uint ? nullptr : ctl_float_words(l, fx), as_uint ? fx->d_ua : nullptr, fx->n);
-  GHIP(ctx, hipGetLastError());
-  return 0;
-}
-static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src);
-static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
-                         uint32_t control_index, groove_ctl_link** out);
-// A trip link: ONE create for the plain and the filter form, by the parameter.
-int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
-                           groove_fx* target, uint32_t control_index, groove_ctl_link** out) {
-  if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, "groove_ctl_trip_create: NULL argument");
-  if (std::find(ctx->fxs.begin(), ctx->fxs.end(), target) == ctx->fxs.end()) return fail(ctx, "groove_ctl_trip_create: the target is not a live effect of this context");
-  if (n_src != 1 && n_src != target->n) return fail(ctx, "groove_ctl_trip_create: n_src must be the target's lane count, or 1 (broadcast)");
-  bool derived = false;
-  switch (control_index) {
-    case GROOVE_CTL_FX_WET:
-      return fail(ctx, "groove_ctl_trip_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
-    case GROOVE_CTL_FX_CUTOFF: case GROOVE_CTL_FX_Q: case GROOVE_CTL_FX_PASSBAND_RIPPLE:
-      if (!ctl_target_derived(target->kind, control_index))
-        return fail(ctx, "groove_ctl_trip_create: the target's kind has no such parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)");
-      derived = true;
-      break;
-    default: {
-      if (!ctl_target_linkable(control_index)) return fail(ctx, "groove_ctl_trip_create: unknown control index");
-      const bool fits = (control_index == GROOVE_CTL_FX_CEILING && target->kind == GROOVE_FX_GAIN) ||
-                        (control_index == GROOVE_CTL_FX_BITS && target->kind == GROOVE_FX_BITCRUSHER) ||
-                        (control_index == GROOVE_CTL_FX_ATTENUATION && target->kind == GROOVE_FX_REVERB) ||
-                        (control_index == GROOVE_CTL_FX_THRESHOLD && (target->kind == GROOVE_FX_COMPRESSOR || target->kind == GROOVE_FX_LIMITER));
-      if (!fits) return fail(ctx, "groove_ctl_trip_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
-    }
-  }
-  if (ctl_trip_check_steps(ctx, "groove_ctl_trip_create", steps, n_steps, start_beat, n_src)) return 1;
-  GHIP(ctx, hipSetDevice(ctx->device));
-  if (derived && !target->d_shadow) { // the first filter link onto this effect: from here on fx_upload_params keeps the shadow beside the coefficients
-    if (hipMalloc(&target->d_shadow, (size_t)CTL_SHADOW_WORDS * target->n * 4) != hipSuccess) {
-      target->d_shadow = nullptr;
-      return fail(ctx, "groove_ctl_trip_create: hipMalloc failed");
-    }
-    if (fx_acquire_ctx(target) || fx_upload_shadow(target)) return 1;
-  }
-  groove_ctl_link* l = nullptr;
-  if (ctl_trip_make(ctx, "groove_ctl_trip_create", steps, n_steps, start_beat, n_src, control_index, &l)) return 1;
-  l->target = target; l->derived = derived;
-  ctx->links.push_back(l);
-  *out = l;
-  return 0;
-}
-// What a trip's create asks of its steps (the effect and the bank form alike).
-static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src) {
-  const std::string w = std::string(who) + ": ";
-  if (n_steps == 0) return fail(ctx, w + "a trip has at least one step");
-  if (n_steps > 65536u) return fail(ctx, w + "more than 65,536 steps");
-  for (uint32_t s = 0; s < n_src; ++s) {
-    if (!std::isfinite(start_beat[s])) return fail(ctx, w + "start_beat is not finite");
-    for (uint32_t i = 0; i < n_steps; ++i) {
-      const groove_ctl_step& st = steps[(size_t)s * n_steps + i];
-      if (!ctl_trip_kind_ok(st.kind)) return fail(ctx, w + "unknown step kind (flat, slope, logarithmic, exponential; `Triggered` has no behaviour)");
-      if (!std::isfinite(st.beats) || !std::isfinite(st.start) || !std::isfinite(st.end)) return fail(ctx, w + "a step's beats, start or end is not finite");
-      if (!(st.beats > 0.0)) return fail(ctx, w + "a step's beats must be > 0");
-    }
-  }
-  return 0;
-}
-// A trip link with its step table on the device and no target yet; the caller sets the target and lists the link.
-static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
-                         uint32_t control_index, groove_ctl_link** out) {
-  const std::string who_s = std::string(who) + ": ";
-  // the table, SoA [step][source lane]
-  const size_t rows = (size_t)n_steps * n_src, doubles = rows * 4 + n_src;
-  std::vector<double> w(doubles + (rows + 1) / 2);
-  double *begin = w.data(), *start = begin + rows + n_src, *end = start + rows, *beats = end + rows;
-  uint32_t* kind = reinterpret_cast<uint32_t*>(beats + rows);
-  for (uint32_t s = 0; s < n_src; ++s) {
-    const groove_ctl_step* st = steps + (size_t)s * n_steps;
-    for (uint32_t i = 0; i < n_steps; ++i) {
-      const size_t at = (size_t)i * n_src + s;
-      start[at] = st[i].start; end[at] = st[i].end; beats[at] = st[i].beats; kind[at] = st[i].kind;
-    }
-    ctl_trip_begins(start_beat[s], beats + s, n_src, n_steps, begin + s, n_src);
-  }
-  groove_ctl_link* l = new groove_ctl_link();
-  l->ctx = ctx; l->source = GROOVE_CTL_SRC_TRIP; l->n_src = n_src; l->control_index = control_index; l->target = nullptr;
-  l->n_steps = n_steps;
-  if (hipMalloc(&l->d_trip, w.size() * 8) != hipSuccess) {
-    l->d_trip = nullptr;
-    groove_ctl_link_destroy(l);
-    return fail(ctx, who_s + "hipMalloc failed");
-  }
-  if (ctx_memcpy(ctx, l->d_trip, w.data(), w.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-    groove_ctl_link_destroy(l);
-    return fail(ctx, who_s + "the upload of the step table failed");
-  }
-  *out = l;
-  return 0;
-}
-int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
-  if (!l) return fail(nullptr, "groove_ctl_trip_apply: link is NULL");
-  groove_ctx* ctx = l->ctx;
-  groove_fx* fx = l->target;
-  if (l->source != GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_trip_apply: not a trip link (an LFO or signal link is applied at a frame: groove_ctl_link_apply)");
-  if (l->on_bank) return bank_link_apply(l, "groove_ctl_trip_apply", at_units);
-  if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, "groove_ctl_trip_apply: the target effect has been destroyed");
-  GHIP(ctx, hipSetDevice(ctx->device));
-  if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
-  const size_t rows = (size_t)l->n_steps * l->n_src;
-  const double *begin = l->d_trip, *start = begin + rows + l->n_src, *end = start + rows, *beats = end + rows;
-  const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
-  if (l->derived) {
-    hipLaunchKernelGGL(ctl_trip_filter_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, fx->kind, l->control_index,
-                       (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n);
-  } else {
-    const bool as_uint = ctl_target_is_uint(l->control_index);
-    hipLaunchKernelGGL(ctl_trip_apply_kernel, dim3(blocks_for(fx->n)), dim3(kThreads), 0, ctx->stream, trip, l->n_src, at_units, as_uint ? nullptr : ctl_float_words(l, fx),
-                       as_uint ? fx->d_ua : nullptr, fx->n);
-  }
-  GHIP(ctx, hipGetLastError());
-  return 0;
+  return fx_acquire_ctx(target) || fx_upload_shadow(target);
 }
 // ---- links onto a bank: a Welsh bank's dca-gain, dca-pan, filter-cutoff; an FM bank's dca-gain, dca-pan, depth, beta; a sampler bank's gain
-// What both bank creates ask of their target.
+// What both bank creates ask of their target, and of n_src for it.
 static int bank_link_check(groove_ctx* ctx, const char* who, groove_bank* b, uint32_t n_src, uint32_t control_index) {
   const std::string w = std::string(who) + ": ";
   if (std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, w + "the target is not a live bank of this context");
   if (b->kind != BANK_WELSH) { // an FM bank's four controls, a sampler (drumkit) bank's gain; one source lane for all voices or one per voice
-    if (ctl_bank_target_ok(control_index)) return fail(ctx, w + "only Welsh banks expose controls 32 - 34 (dca-gain, dca-pan, filter-cutoff)");
+    if (ctl_bank_route(BANK_WELSH, control_index)) return fail(ctx, w + "only Welsh banks expose controls 32 - 34 (dca-gain, dca-pan, filter-cutoff)");
     const bool fm = b->kind == BANK_FM;
-    if (fm ? !ctl_fm_target_ok(control_index) : !ctl_sampler_target_ok(control_index)) {
-      if (fm ? ctl_sampler_target_ok(control_index) : ctl_fm_target_ok(control_index))
+    if (!ctl_bank_route(b->kind, control_index)) {
+      if (ctl_bank_route(fm ? BANK_SAMPLER : BANK_FM, control_index))
         return fail(ctx, w + (fm ? "an FM bank's controls are 48 - 51 (dca-gain, dca-pan, depth, beta); 64 is a sampler bank's gain"
                                  : "a sampler bank's control is 64 (gain); 48 - 51 are an FM bank's"));
       return fail(ctx, w + (fm ? "unknown control index (a link onto an FM bank reaches dca-gain, dca-pan, depth or beta)"
@@ -3232,7 +2990,7 @@ static int bank_link_check(groove_ctx* ctx, const char* who, groove_bank* b, uin
     if (n_src != 1 && n_src != b->n) return fail(ctx, w + "n_src must be the bank's voice count, or 1 (broadcast)");
     return 0;
   }
-  if (!ctl_bank_target_ok(control_index)) return fail(ctx, w + "unknown control index (a bank link reaches dca-gain, dca-pan or filter-cutoff)");
+  if (!ctl_bank_route(BANK_WELSH, control_index)) return fail(ctx, w + "unknown control index (a bank link reaches dca-gain, dca-pan or filter-cutoff)");
   if (n_src != 1)
     return fail(ctx, w + "n_src must be 1: the value is broadcast to every voice (a per-voice source would break the wave-uniform parameter records; per-voice changes keep groove_bank_set_param)");
   return 0;
@@ -3257,81 +3015,262 @@ static int bank_replan(groove_bank* b) {
   b->ctx_touched = true;
   return welsh_upload_params(b, false);
 }
-// The new link `l` onto `b`: listed with the bank; the first cutoff link takes WF_FILTER_F32 off the bank's records.
-static int bank_link_attach(groove_ctl_link* l, groove_bank* b) {
-  l->bank = b; l->on_bank = true;
-  if (l->control_index == GROOVE_CTL_WELSH_CUTOFF && b->cutoff_links++ == 0 && b->ctx->f32_filter && bank_replan(b)) {
+// The source half of a link, with no target yet (link_attach gives it one and lists it): an LFO's or a signal's lanes ...
+static int ctl_link_check_sources(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src) {
+  const std::string w = std::string(who) + ": ";
+  for (uint32_t i = 0; i < n_src; ++i) {
+    if (src[i].source != GROOVE_CTL_SRC_LFO && src[i].source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, w + "unknown source kind");
+    if (src[i].source != src[0].source) return fail(ctx, w + "the lanes of one link share one source kind");
+    if (src[i].source == GROOVE_CTL_SRC_LFO) {
+      if (!ctl_lfo_waveform_ok(src[i].waveform))
+        return fail(ctx, w + "an LFO source is sine, triangle, square, sawtooth, pulse-width or triangle-sine (a noise generator's state at a block start has no closed form)");
+      if (!(src[i].frequency_hz >= 0.0) || !(src[i].frequency_hz < (double)ctx->sr)) return fail(ctx, w + "LFO frequency outside [0, sample rate)");
+    } else if (!ctl_signal_law_ok(src[i].law)) {
+      return fail(ctx, w + "unknown signal law");
+    }
+  }
+  return 0;
+}
+static int ctl_link_make(groove_ctx* ctx, const char* who, const groove_ctl_source* src, uint32_t n_src, uint32_t control_index, groove_ctl_link** out) {
+  const std::string w = std::string(who) + ": ";
+  GHIP(ctx, hipSetDevice(ctx->device));
+  groove_ctl_link* l = new groove_ctl_link();
+  l->ctx = ctx; l->source = src[0].source; l->n_src = n_src; l->control_index = control_index; l->target = nullptr;
+  l->src.assign(src, src + n_src);
+  if (hipMalloc(&l->d_lanes, ctl_lanes_layout(n_src).bytes) != hipSuccess || hipMalloc(&l->d_value, (size_t)n_src * 4) != hipSuccess ||
+      hipMalloc(&l->d_captured, 4) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, w + "hipMalloc failed");
+  }
+  if (hipMemsetAsync(l->d_value, 0, (size_t)n_src * 4, ctx->stream) != hipSuccess || hipMemsetAsync(l->d_captured, 0, 4, ctx->stream) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, w + "hipMemsetAsync failed");
+  }
+  if (ctl_upload_lanes(l)) { groove_ctl_link_destroy(l); return 1; } // (its message stands)
+  *out = l;
+  return 0;
+}
+// ... or a trip's step table (the effect and the bank form alike).
+static int ctl_trip_check_steps(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src) {
+  const std::string w = std::string(who) + ": ";
+  if (n_steps == 0) return fail(ctx, w + "a trip has at least one step");
+  if (n_steps > 65536u) return fail(ctx, w + "more than 65,536 steps");
+  for (uint32_t s = 0; s < n_src; ++s) {
+    if (!std::isfinite(start_beat[s])) return fail(ctx, w + "start_beat is not finite");
+    for (uint32_t i = 0; i < n_steps; ++i) {
+      const groove_ctl_step& st = steps[(size_t)s * n_steps + i];
+      if (!ctl_trip_kind_ok(st.kind)) return fail(ctx, w + "unknown step kind (flat, slope, logarithmic, exponential; `Triggered` has no behaviour)");
+      if (!std::isfinite(st.beats) || !std::isfinite(st.start) || !std::isfinite(st.end)) return fail(ctx, w + "a step's beats, start or end is not finite");
+      if (!(st.beats > 0.0)) return fail(ctx, w + "a step's beats must be > 0");
+    }
+  }
+  return 0;
+}
+static int ctl_trip_make(groove_ctx* ctx, const char* who, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                         uint32_t control_index, groove_ctl_link** out) {
+  const std::string who_s = std::string(who) + ": ";
+  GHIP(ctx, hipSetDevice(ctx->device));
+  const CtlTripLayout lay = ctl_trip_layout(n_src, n_steps);
+  std::vector<double> w(lay.bytes / 8);
+  double *begin = ctl_section<double>(w.data(), lay.begin), *start = ctl_section<double>(w.data(), lay.start), *end = ctl_section<double>(w.data(), lay.end),
+         *beats = ctl_section<double>(w.data(), lay.beats);
+  uint32_t* kind = ctl_section<uint32_t>(w.data(), lay.kind);
+  for (uint32_t s = 0; s < n_src; ++s) {
+    const groove_ctl_step* st = steps + (size_t)s * n_steps;
+    for (uint32_t i = 0; i < n_steps; ++i) {
+      const size_t at = (size_t)i * n_src + s;
+      start[at] = st[i].start; end[at] = st[i].end; beats[at] = st[i].beats; kind[at] = st[i].kind;
+    }
+    ctl_trip_begins(start_beat[s], beats + s, n_src, n_steps, begin + s, n_src);
+  }
+  groove_ctl_link* l = new groove_ctl_link();
+  l->ctx = ctx; l->source = GROOVE_CTL_SRC_TRIP; l->n_src = n_src; l->control_index = control_index; l->target = nullptr;
+  l->n_steps = n_steps;
+  if (hipMalloc(&l->d_trip, lay.bytes) != hipSuccess) {
+    l->d_trip = nullptr;
+    groove_ctl_link_destroy(l);
+    return fail(ctx, who_s + "hipMalloc failed");
+  }
+  if (ctx_memcpy(ctx, l->d_trip, w.data(), lay.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    groove_ctl_link_destroy(l);
+    return fail(ctx, who_s + "the upload of the step table failed");
+  }
+  *out = l;
+  return 0;
+}
+// The finished source half `l` gets its target — an effect or a bank — and is listed with the context.  A reverb counts its wet links
+// (fx_needs_dry); the first cutoff link takes WF_FILTER_F32 off a Welsh bank's records.  groove_ctl_link_destroy unwinds all of it.
+static int link_attach(groove_ctl_link* l, groove_fx* fx, groove_bank* b, groove_ctl_link** out) {
+  groove_ctx* ctx = l->ctx;
+  l->target = fx; l->bank = b; l->on_bank = b != nullptr;
+  ctx->links.push_back(l);
+  if (fx && l->control_index == GROOVE_CTL_FX_WET) ++fx->wet_links;
+  if (b && l->control_index == GROOVE_CTL_WELSH_CUTOFF && b->cutoff_links++ == 0 && ctx->f32_filter && bank_replan(b)) {
     groove_ctl_link_destroy(l);
     return 1;
   }
+  *out = l;
   return 0;
+}
+
+int groove_ctl_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                           groove_ctl_link** out) {
+  const char* who = "groove_ctl_link_create";
+  if (fx_link_check(ctx, who, src != nullptr, n_src, target, out)) return 1;
+  switch (ctl_fx_class(control_index)) {
+    case CTL_ROUTE_DERIVED:
+      return fail(ctx, "groove_ctl_link_create: cutoff, q and passband-ripple become filter coefficients on the host (f64): not linkable on the device; use groove_fx_set_param");
+    case CTL_ROUTE_WET:
+      return fail(ctx, "groove_ctl_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+    case CTL_ROUTE_FLOAT: case CTL_ROUTE_UINT: break;
+    default: return fail(ctx, "groove_ctl_link_create: unknown control index");
+  }
+  if (!ctl_fx_route(target->kind, control_index))
+    return fail(ctx, "groove_ctl_link_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
+  groove_ctl_link* l = nullptr;
+  if (ctl_link_check_sources(ctx, who, src, n_src) || ctl_link_make(ctx, who, src, n_src, control_index, &l)) return 1;
+  return link_attach(l, target, nullptr, out);
+}
+int groove_ctl_filter_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, uint32_t control_index,
+                                  groove_ctl_link** out) {
+  const char* who = "groove_ctl_filter_link_create";
+  if (fx_link_check(ctx, who, src != nullptr, n_src, target, out)) return 1;
+  switch (ctl_fx_class(control_index)) {
+    case CTL_ROUTE_DERIVED: break;
+    case CTL_ROUTE_WET:
+      return fail(ctx, "groove_ctl_filter_link_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+    case CTL_ROUTE_FLOAT: case CTL_ROUTE_UINT:
+      return fail(ctx, "groove_ctl_filter_link_create: a filter link reaches cutoff, q or passband-ripple; this parameter's device form is the value itself: use groove_ctl_link_create");
+    default:
+      return fail(ctx, "groove_ctl_filter_link_create: unknown control index (a filter link reaches cutoff, q or passband-ripple)");
+  }
+  if (!ctl_fx_route(target->kind, control_index))
+    return fail(ctx, "groove_ctl_filter_link_create: the target's kind does not derive its coefficients from that parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)");
+  groove_ctl_link* l = nullptr;
+  if (ctl_link_check_sources(ctx, who, src, n_src) || fx_ensure_shadow(target, who) || ctl_link_make(ctx, who, src, n_src, control_index, &l)) return 1;
+  return link_attach(l, target, nullptr, out);
+}
+int groove_ctl_wet_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_fx* target, groove_ctl_link** out) {
+  const char* who = "groove_ctl_wet_link_create";
+  groove_ctl_link* l = nullptr;
+  if (fx_link_check(ctx, who, src != nullptr, n_src, target, out) || wet_link_check_target(ctx, who, target) || ctl_link_check_sources(ctx, who, src, n_src) ||
+      ctl_link_make(ctx, who, src, n_src, GROOVE_CTL_FX_WET, &l))
+    return 1;
+  return link_attach(l, target, nullptr, out);
+}
+// A trip link: ONE create for the plain and the filter form, by the parameter.
+int groove_ctl_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
+                           groove_fx* target, uint32_t control_index, groove_ctl_link** out) {
+  const char* who = "groove_ctl_trip_create";
+  if (fx_link_check(ctx, who, steps && start_beat, n_src, target, out)) return 1;
+  const CtlRoute cls = ctl_fx_class(control_index);
+  if (cls == CTL_ROUTE_WET) return fail(ctx, "groove_ctl_trip_create: wet-dry-mix chooses a kernel path on the host: not linkable on the device; use groove_fx_set_param");
+  if (cls == CTL_ROUTE_NONE) return fail(ctx, "groove_ctl_trip_create: unknown control index");
+  if (!ctl_fx_route(target->kind, control_index))
+    return fail(ctx, cls == CTL_ROUTE_DERIVED
+                         ? "groove_ctl_trip_create: the target's kind has no such parameter (cutoff: the nine filter kinds; q: low-pass, high-pass and all-pass 12 dB; passband-ripple: low-pass 24 dB)"
+                         : "groove_ctl_trip_create: the target's kind has no such parameter (ceiling: Gain; bits: Bitcrusher; attenuation: Reverb; threshold: Compressor / Limiter)");
+  groove_ctl_link* l = nullptr;
+  if (ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src) || (cls == CTL_ROUTE_DERIVED && fx_ensure_shadow(target, who)) ||
+      ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, control_index, &l))
+    return 1;
+  return link_attach(l, target, nullptr, out);
+}
+int groove_ctl_wet_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src, groove_fx* target,
+                               groove_ctl_link** out) {
+  const char* who = "groove_ctl_wet_trip_create";
+  groove_ctl_link* l = nullptr;
+  if (fx_link_check(ctx, who, steps && start_beat, n_src, target, out) || wet_link_check_target(ctx, who, target) ||
+      ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src) || ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, GROOVE_CTL_FX_WET, &l))
+    return 1;
+  return link_attach(l, target, nullptr, out);
 }
 int groove_ctl_bank_link_create(groove_ctx* ctx, const groove_ctl_source* src, uint32_t n_src, groove_bank* target, uint32_t control_index,
                                 groove_ctl_link** out) {
   const char* who = "groove_ctl_bank_link_create";
   if (!ctx || !src || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
-  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_link_check_sources(ctx, who, src, n_src)) return 1;
-  if (bank_link_prepare(target, who, control_index)) return 1;
   groove_ctl_link* l = nullptr;
-  if (ctl_link_make(ctx, who, src, n_src, nullptr, control_index, false, &l)) return 1;
-  if (bank_link_attach(l, target)) return 1;
-  *out = l;
-  return 0;
+  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_link_check_sources(ctx, who, src, n_src) || bank_link_prepare(target, who, control_index) ||
+      ctl_link_make(ctx, who, src, n_src, control_index, &l))
+    return 1;
+  return link_attach(l, nullptr, target, out);
 }
 int groove_ctl_bank_trip_create(groove_ctx* ctx, const groove_ctl_step* steps, uint32_t n_steps, const double* start_beat, uint32_t n_src,
                                 groove_bank* target, uint32_t control_index, groove_ctl_link** out) {
   const char* who = "groove_ctl_bank_trip_create";
   if (!ctx || !steps || !start_beat || !target || !out) return fail(ctx, std::string(who) + ": NULL argument");
-  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src)) return 1;
-  if (bank_link_prepare(target, who, control_index)) return 1;
   groove_ctl_link* l = nullptr;
-  if (ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, control_index, &l)) return 1;
-  ctx->links.push_back(l);
-  if (bank_link_attach(l, target)) return 1;
-  *out = l;
+  if (bank_link_check(ctx, who, target, n_src, control_index) || ctl_trip_check_steps(ctx, who, steps, n_steps, start_beat, n_src) ||
+      bank_link_prepare(target, who, control_index) || ctl_trip_make(ctx, who, steps, n_steps, start_beat, n_src, control_index, &l))
+    return 1;
+  return link_attach(l, nullptr, target, out);
+}
+int groove_ctl_link_capture(groove_ctl_link* l, groove_block* blk, uint32_t frames) {
+  if (!l || !blk) return fail(nullptr, "groove_ctl_link_capture: NULL argument");
+  groove_ctx* ctx = l->ctx;
+  if (blk->ctx != ctx) return fail(ctx, "groove_ctl_link_capture: link and block belong to different contexts");
+  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(ctx, "groove_ctl_link_capture: a trip link captures nothing (groove_ctl_trip_apply is its only call)");
+  if (l->source != GROOVE_CTL_SRC_SIGNAL) return fail(ctx, "groove_ctl_link_capture: not a signal link");
+  if (blk->n != l->n_src) return fail(ctx, "groove_ctl_link_capture: block lanes != source lanes");
+  if (frames > blk->cap) return fail(ctx, "groove_ctl_link_capture: frames > block capacity");
+  if (frames == 0) return 0; // nothing has been transformed
+  GHIP(ctx, hipSetDevice(ctx->device));
+  if (block_acquire(blk) || block_normalise(blk)) return 1; // the source lanes are in the caller's order, like an effect's
+  hipLaunchKernelGGL(ctl_capture_kernel, dim3(blocks_for(blk->n)), dim3(kThreads), 0, ctx->stream, blk->d, (size_t)blk->cap * blk->n, blk->n, frames - 1,
+                     l->d_value, l->d_captured);
+  GHIP(ctx, hipGetLastError());
   return 0;
 }
-// groove_ctl_link_apply / groove_ctl_trip_apply on a bank link.  The bank's renders run on side streams: the ctx stream joins them by
-// events (no host wait), the kernel runs there, and every later render of the bank forks behind it (ctx_join: need_fork; ctx_touched
+// groove_ctl_link_apply / groove_ctl_trip_apply: which target, order the ctx stream against its other users, one launch of the apply
+// kernel by (source, target).  An effect: fx_acquire_ctx + fx_ap_settle.  A bank's renders run on side streams: the ctx stream joins them
+// by events (no host wait), the kernel runs there, and every later render of the bank forks behind it (ctx_join: need_fork; ctx_touched
 // for the asynchronous render's own choice of what to wait for) — no render of the bank overlaps the write of its records.
-static int bank_link_apply(groove_ctl_link* l, const char* who, uint64_t at) {
+static int link_apply(groove_ctl_link* l, const char* who, uint64_t at) {
   groove_ctx* ctx = l->ctx;
+  groove_fx* fx = l->target;
   groove_bank* b = l->bank;
-  if (!b || std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, std::string(who) + ": the target bank has been destroyed");
-  GHIP(ctx, hipSetDevice(ctx->device));
-  b->ctx_touched = true;
-  if (ctx_join(ctx)) return 1;
-  if (b->kind != BANK_WELSH) { // one thread per voice onto the per-voice SoA, the one place every FM and sampler kernel reads (ctl_link.h)
-    const uint32_t ns = l->n_src;
-    const CtlVoices voices{b->d_params, b->kind == BANK_FM ? b->d_dca : nullptr, b->n, l->control_index};
-    const dim3 vgrid(blocks_for(b->n));
-    if (l->source == GROOVE_CTL_SRC_TRIP) {
-      const size_t rows = (size_t)l->n_steps * ns;
-      const double *begin = l->d_trip, *start = begin + rows + ns, *end = start + rows, *beats = end + rows;
-      const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
-      hipLaunchKernelGGL(ctl_trip_voices_apply_kernel, vgrid, dim3(kThreads), 0, ctx->stream, trip, ns, at, voices);
-    } else {
-      const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + (size_t)2 * ns);
-      const CtlLanes lanes{l->d_lanes, l->d_lanes + ns, u, u + ns};
-      hipLaunchKernelGGL(ctl_voices_apply_kernel, vgrid, dim3(kThreads), 0, ctx->stream, l->source, lanes, ns, at, l->d_value, l->d_captured, voices);
-    }
-    GHIP(ctx, hipGetLastError());
-    return 0;
-  }
-  const CtlBank bank{b->d_params, b->plan.n_vwaves ? b->d_waves : nullptr, b->d_dca, b->n, b->plan.n_vwaves, l->control_index};
-  const dim3 grid(blocks_for(std::max<size_t>(b->n, b->plan.n_vwaves)));
-  if (l->source == GROOVE_CTL_SRC_TRIP) {
-    const size_t rows = (size_t)l->n_steps;
-    const double *begin = l->d_trip, *start = begin + rows + 1, *end = start + rows, *beats = end + rows;
-    const CtlTrip trip{begin, start, end, beats, reinterpret_cast<const uint32_t*>(beats + rows), l->n_steps};
-    hipLaunchKernelGGL(ctl_trip_bank_apply_kernel, grid, dim3(kThreads), 0, ctx->stream, trip, at, bank);
+  if (l->on_bank) {
+    if (!b || std::find(ctx->banks.begin(), ctx->banks.end(), b) == ctx->banks.end()) return fail(ctx, std::string(who) + ": the target bank has been destroyed");
+    GHIP(ctx, hipSetDevice(ctx->device));
+    b->ctx_touched = true;
+    if (ctx_join(ctx)) return 1;
   } else {
-    const uint32_t* u = reinterpret_cast<const uint32_t*>(l->d_lanes + 2);
-    const CtlLanes lanes{l->d_lanes, l->d_lanes + 1, u, u + 1};
-    hipLaunchKernelGGL(ctl_bank_apply_kernel, grid, dim3(kThreads), 0, ctx->stream, l->source, lanes, at, l->d_value, l->d_captured, bank);
+    if (!fx || std::find(ctx->fxs.begin(), ctx->fxs.end(), fx) == ctx->fxs.end()) return fail(ctx, std::string(who) + ": the target effect has been destroyed");
+    GHIP(ctx, hipSetDevice(ctx->device));
+    if (fx_acquire_ctx(fx) || fx_ap_settle(fx)) return 1;
+  }
+  auto launch = [&](const auto& source, const auto& target) {
+    using Source = std::decay_t<decltype(source)>;
+    using Target = std::decay_t<decltype(target)>;
+    hipLaunchKernelGGL((ctl_apply_kernel<Source, Target>), dim3(blocks_for(target.threads())), dim3(kThreads), 0, ctx->stream, source, target);
+  };
+  auto from_source = [&](const auto& target) {
+    if (l->source == GROOVE_CTL_SRC_TRIP) launch(CtlTripAt{ctl_trip_view(l), l->n_src, at}, target);
+    else launch(CtlLive{l->source, l->n_src, ctl_lanes_view(l), at, l->d_value, l->d_captured}, target);
+  };
+  if (l->on_bank) { // a Welsh bank's records and per-wave copies; an FM or sampler bank's per-voice SoA, the one place its kernels read (ctl_link.h)
+    if (b->kind == BANK_WELSH) from_source(CtlBank{b->d_params, b->plan.n_vwaves ? b->d_waves : nullptr, b->d_dca, b->n, b->plan.n_vwaves, l->control_index});
+    else from_source(CtlVoices{b->d_params, b->kind == BANK_FM ? b->d_dca : nullptr, b->n, l->control_index});
+  } else {
+    switch (ctl_fx_route(fx->kind, l->control_index)) {
+      case CTL_ROUTE_DERIVED: from_source(CtlFilter{fx->kind, l->control_index, (double)ctx->sr, fx->d_shadow, fx->d_coef, fx->n}); break;
+      case CTL_ROUTE_UINT: from_source(CtlPlain{nullptr, fx->d_ua, fx->n}); break;
+      case CTL_ROUTE_WET: from_source(CtlPlain{fx->d_wet, nullptr, fx->n}); break;
+      default: from_source(CtlPlain{fx->d_fa, nullptr, fx->n}); break;
+    }
   }
   GHIP(ctx, hipGetLastError());
   return 0;
+}
+int groove_ctl_link_apply(groove_ctl_link* l, uint64_t at_frame) {
+  if (!l) return fail(nullptr, "groove_ctl_link_apply: link is NULL");
+  if (l->source == GROOVE_CTL_SRC_TRIP) return fail(l->ctx, "groove_ctl_link_apply: a trip link is applied at a musical time: use groove_ctl_trip_apply");
+  return link_apply(l, "groove_ctl_link_apply", at_frame);
+}
+int groove_ctl_trip_apply(groove_ctl_link* l, uint64_t at_units) {
+  if (!l) return fail(nullptr, "groove_ctl_trip_apply: link is NULL");
+  if (l->source != GROOVE_CTL_SRC_TRIP) return fail(l->ctx, "groove_ctl_trip_apply: not a trip link (an LFO or signal link is applied at a frame: groove_ctl_link_apply)");
+  return link_apply(l, "groove_ctl_trip_apply", at_units);
 }
 int groove_ctl_link_reset(groove_ctl_link* l) {
   if (!l) return fail(nullptr, "groove_ctl_link_reset: link is NULL");
@@ -3344,7 +3283,7 @@ int groove_ctl_link_reset(groove_ctl_link* l) {
 int groove_ctl_link_destroy(groove_ctl_link* l) {
   if (!l) return 0;
   groove_ctx* ctx = l->ctx;
-  // the last cutoff link off a live bank: its records may carry WF_FILTER_F32 again (bank_link_attach)
+  // the last cutoff link off a live bank: its records may carry WF_FILTER_F32 again (link_attach)
   if (l->bank && l->control_index == GROOVE_CTL_WELSH_CUTOFF && std::find(ctx->banks.begin(), ctx->banks.end(), l->bank) != ctx->banks.end() &&
       l->bank->cutoff_links && --l->bank->cutoff_links == 0 && ctx->f32_filter)
     (void)bank_replan(l->bank);

@@ -1,7 +1,6 @@
 // groove_host.cpp — see groove_host.hpp.  Every audio operation goes through the C ABI of
 // libgroove_hip.so; there is no CPU audio path here.
 #include "groove_host.hpp"
-#include "../csrc/ctl_core.h" // the control links' value laws, for the links the host evaluates itself
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -440,8 +439,8 @@ void Orchestrator::place_trips() {
       return instrument_controls_on_device_ && bank_control_device_linkable(static_cast<Instrument*>(get(t->target()))->bank_controls(), (int)t->control_index());
     if (!trips_on_device_ || !fx_of(t->target())) return false;
     const uint32_t kind = static_cast<FxEffect*>(get(t->target()))->kind();
-    return fx_control_device_linkable(kind, (int)t->control_index()) || fx_control_device_derived(kind, (int)t->control_index()) ||
-           (wet_links_on_device_ && fx_control_device_wet(kind, (int)t->control_index()));
+    const groove::CtlRoute route = fx_control_route(kind, (int)t->control_index());
+    return route != groove::CTL_ROUTE_NONE && (route != groove::CTL_ROUTE_WET || wet_links_on_device_);
   };
   // the effects and instruments that ANY control reaches through the host: a trip the library cannot take, a `controls` link without a device link
   std::vector<char> host_path(nodes_.size(), 0);
@@ -481,33 +480,21 @@ int Orchestrator::link_control(Uid source, Uid target, const std::string& param)
   if (idx < 0) return fail("link_control: unknown control name " + param);
   const groove_ctl_source desc = src->source_desc();
   groove_fx* fx = te->is_effect() ? static_cast<Effect*>(te)->library_fx() : nullptr;
-  if (fx && fx_control_device_linkable(static_cast<FxEffect*>(te)->kind(), idx)) {
-    groove_ctl_link* link = nullptr;
-    if (groove_ctl_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link)) return fail(groove_last_error(ctx_));
-    src->add_link({link, target, (uint32_t)idx});
-    return 0;
-  }
-  if (fx && filter_links_on_device_ && fx_control_device_derived(static_cast<FxEffect*>(te)->kind(), idx)) {
-    groove_ctl_link* link = nullptr;
-    if (groove_ctl_filter_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link)) return fail(groove_last_error(ctx_));
-    src->add_link({link, target, (uint32_t)idx});
-    return 0;
-  }
-  if (fx && wet_links_on_device_ && fx_control_device_wet(static_cast<FxEffect*>(te)->kind(), idx)) {
-    groove_ctl_link* link = nullptr;
-    if (groove_ctl_wet_link_create(ctx_, &desc, 1, fx, &link)) return fail(groove_last_error(ctx_));
-    src->add_link({link, target, (uint32_t)idx});
-    return 0;
-  }
   groove_bank* bank = te->is_instrument() ? static_cast<Instrument*>(te)->fused_bank() : nullptr;
-  if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(static_cast<Instrument*>(te)->bank_controls(), idx)) {
-    groove_ctl_link* link = nullptr;
-    if (!groove_ctl_bank_link_create(ctx_, &desc, 1, bank, (uint32_t)idx, &link)) {
-      src->add_link({link, target, (uint32_t)idx, true});
-      return 0;
-    }
-    // (the library refuses: a noise LFO — the host path below, with its own checks)
+  // which create, if any, keeps this link on the device: the route of (target kind, parameter), and the orchestrator's switches
+  const groove::CtlRoute route = fx ? fx_control_route(static_cast<FxEffect*>(te)->kind(), idx) : groove::CTL_ROUTE_NONE;
+  groove_ctl_link* link = nullptr;
+  int rc = -1; // -1: no create was tried
+  if (route == groove::CTL_ROUTE_FLOAT || route == groove::CTL_ROUTE_UINT) rc = groove_ctl_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link);
+  else if (route == groove::CTL_ROUTE_DERIVED && filter_links_on_device_) rc = groove_ctl_filter_link_create(ctx_, &desc, 1, fx, (uint32_t)idx, &link);
+  else if (route == groove::CTL_ROUTE_WET && wet_links_on_device_) rc = groove_ctl_wet_link_create(ctx_, &desc, 1, fx, &link);
+  else if (bank && instrument_controls_on_device_ && desc.source == GROOVE_CTL_SRC_LFO && bank_control_device_linkable(static_cast<Instrument*>(te)->bank_controls(), idx))
+    rc = groove_ctl_bank_link_create(ctx_, &desc, 1, bank, (uint32_t)idx, &link);
+  if (rc == 0) {
+    src->add_link({link, target, (uint32_t)idx, bank != nullptr});
+    return 0;
   }
+  if (rc > 0 && !bank) return fail(groove_last_error(ctx_)); // (a bank link the library refuses — a noise LFO: the host path below, with its own checks)
   if (desc.source == GROOVE_CTL_SRC_SIGNAL) {
     err_ = "link_control: a signal source onto '" + param + "' would need a download per block (the host derives that parameter's device form); dropped";
     return 2;

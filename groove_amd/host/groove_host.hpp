@@ -24,6 +24,7 @@
 // the fan-in test :1642-1668); sources with more lanes than the sink are lane-summed.
 #pragma once
 #include "../../include/groove_hip.h"
+#include "../csrc/ctl_core.h" // the control links' route table (ctl_fx_route, ctl_bank_route) and value laws
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -114,33 +115,23 @@ inline BankControls bank_controls_of_device(const std::string& device_kind) {
 // them (tests/test_project_controllers.py), nothing more is built for it.
 inline bool bank_control_device_linkable(BankControls kind, int index) {
   switch (kind) {
-    case BankControls::WELSH: return index == GROOVE_CTL_WELSH_DCA_GAIN || index == GROOVE_CTL_WELSH_DCA_PAN || index == GROOVE_CTL_WELSH_CUTOFF;
-    case BankControls::FM: return index >= GROOVE_CTL_FM_DCA_GAIN && index <= GROOVE_CTL_FM_BETA;
-    case BankControls::SAMPLER: return index == GROOVE_CTL_SAMPLER_GAIN;
+    case BankControls::WELSH: return groove::ctl_bank_route(groove::BANK_WELSH, (uint32_t)index) != groove::CTL_ROUTE_NONE;
+    case BankControls::FM: return groove::ctl_bank_route(groove::BANK_FM, (uint32_t)index) != groove::CTL_ROUTE_NONE;
+    case BankControls::SAMPLER: return groove::ctl_bank_route(groove::BANK_SAMPLER, (uint32_t)index) != groove::CTL_ROUTE_NONE;
     default: return false;
   }
 }
-// Can a control link onto this parameter of this kind of effect stay on the device (groove_ctl_link_create: the parameters whose device
-// form IS the value, on the kind whose kernels read them)?  (A filter's cutoff, q and passband-ripple can too, through a filter link, where
-// the orchestrator has been asked to: Orchestrator::set_filter_links_on_device, fx_control_device_derived below.)
+// How a control link onto this parameter of this kind of effect can stay on the device (ctl_core.h: ctl_fx_route; the creates have the
+// last word).  linkable: the parameters whose device form IS the value, on the kind whose kernels read them (groove_ctl_link_create).
+// derived: a filter's cutoff, q and passband-ripple, through a filter link, where the orchestrator has been asked to
+// (Orchestrator::set_filter_links_on_device).  wet: wet-dry-mix onto every kind but the Mixer, which launches nothing
+// (groove_ctl_wet_link_create / groove_ctl_wet_trip_create), where asked to (Orchestrator::set_wet_links_on_device).
+inline groove::CtlRoute fx_control_route(uint32_t fx_kind, int index) { return groove::ctl_fx_route(fx_kind, (uint32_t)index); }
 inline bool fx_control_device_linkable(uint32_t fx_kind, int index) {
-  return (index == GROOVE_CTL_FX_CEILING && fx_kind == GROOVE_FX_GAIN) || (index == GROOVE_CTL_FX_BITS && fx_kind == GROOVE_FX_BITCRUSHER) ||
-         (index == GROOVE_CTL_FX_ATTENUATION && fx_kind == GROOVE_FX_REVERB) ||
-         (index == GROOVE_CTL_FX_THRESHOLD && (fx_kind == GROOVE_FX_COMPRESSOR || fx_kind == GROOVE_FX_LIMITER));
+  return fx_control_route(fx_kind, index) == groove::CTL_ROUTE_FLOAT || fx_control_route(fx_kind, index) == groove::CTL_ROUTE_UINT;
 }
-
-// The parameters a FILTER link reaches (groove_ctl_filter_link_create, which has the last word): cutoff onto the nine filter kinds, q onto the
-// kinds whose formula reads it, passband-ripple onto the 24 dB low-pass.
-// wet-dry-mix onto every kind whose kernels read it (groove_ctl_wet_link_create / groove_ctl_wet_trip_create, which have the last word): all
-// but the Mixer, which launches nothing.  Only where the orchestrator has been asked to: Orchestrator::set_wet_links_on_device.
-inline bool fx_control_device_wet(uint32_t fx_kind, int index) { return index == GROOVE_CTL_FX_WET && fx_kind != GROOVE_FX_MIXER; }
-inline bool fx_control_device_derived(uint32_t fx_kind, int index) {
-  const bool lp24 = fx_kind == GROOVE_FX_BIQUAD_LP24;
-  const bool bq12 = fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || (fx_kind >= GROOVE_FX_BIQUAD_BP12 && fx_kind <= GROOVE_FX_BIQUAD_HSHELF12);
-  if (index == GROOVE_CTL_FX_CUTOFF) return lp24 || bq12;
-  if (index == GROOVE_CTL_FX_Q) return fx_kind == GROOVE_FX_BIQUAD_LP12 || fx_kind == GROOVE_FX_BIQUAD_HP12 || fx_kind == GROOVE_FX_BIQUAD_AP12;
-  return index == GROOVE_CTL_FX_PASSBAND_RIPPLE && lp24;
-}
+inline bool fx_control_device_wet(uint32_t fx_kind, int index) { return fx_control_route(fx_kind, index) == groove::CTL_ROUTE_WET; }
+inline bool fx_control_device_derived(uint32_t fx_kind, int index) { return fx_control_route(fx_kind, index) == groove::CTL_ROUTE_DERIVED; }
 
 // IsInstrument: Generates<StereoSample> + Ticks + HandlesMidi.
 class Instrument : public Entity {
