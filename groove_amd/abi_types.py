@@ -71,6 +71,12 @@ class SampleLoop(C.Structure):
     _fields_ = [("start", C.c_uint32), ("end", C.c_uint32)]
 
 
+# groove_bank_set_sample_envelopes takes EnvelopeParams (above), one per sample; groove_bank_download_sample_envelope_state gives these
+# words per voice, word-major [7][n]
+SAMPLE_ENV_STATE_WORDS = ("state", "n", "N", "A", "D", "inv_len", "value")
+ENV_IDLE, ENV_ATTACK, ENV_DECAY, ENV_SUSTAIN, ENV_RELEASE = range(5)
+
+
 class SamplerParams(C.Structure):
     _fields_ = [("sample_index", C.c_uint32), ("one_shot", C.c_uint32), ("gain", C.c_float)]
 

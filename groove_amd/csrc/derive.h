@@ -220,6 +220,18 @@ GROOVE_HD void sampler_note(const SamplerParams& p, SamplerState& s, uint32_t ke
     s.playing = 0;
   }
 }
+// The note rule of a bank with envelopes (dsp_core.h sampler_voice_enveloped; docs/DSP_SPEC.md section 7).  Note-on is sampler_note's
+// and then attacks, a retrigger from the current value as for Welsh and FM voices; note-off releases and leaves playing, idx and step
+// alone: the voice stops when its release has ended (sampler_frame_env).  A voice without an envelope: sampler_note.
+GROOVE_HD void sampler_note_env(const SamplerParams& p, const EnvParams& ep, SamplerState& s, EnvState& es, uint32_t key, bool on) {
+  if (!sampler_voice_enveloped(p, ep)) { sampler_note(p, s, key, on); return; }
+  if (on) {
+    sampler_note(p, s, key, true);
+    env_trigger_attack(es, ep);
+  } else {
+    env_trigger_release(es, ep);
+  }
+}
 
 // f64 coefficient sets for the effect kernels (identical to the oracle's math).  The formulas are fx_coef.h's, one text for the
 // host and for the device's filter links; these are the host's names for them.

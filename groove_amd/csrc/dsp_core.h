@@ -1633,7 +1633,7 @@ GROOVE_HD void sampler_frame_loop_stereo(const SamplerParams& p, const SampleLoo
 // sampler_chunk_interp / sampler_chunk_interp_stereo on a bank with loops: one text for the voices that loop and those that do not
 // (lanes of one wavefront are voices of both kinds), frame k at its closed-form position, all C * N fetches issued before any is used.
 template <int MODE, int C>
-GROOVE_HD void sampler_chunk_loop(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const float* bank, uint32_t count, float (&v)[C]) {
+GROOVE_HD uint32_t sampler_chunk_loop(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const float* bank, uint32_t count, float (&v)[C]) { // returns `valid`
   using T = SampleTaps<MODE>;
   const bool loops = sampler_voice_loops(p, s, lp);
   const uint32_t ls = loops ? lp.start : 0u, le = loops ? lp.end : 0u;
@@ -1661,9 +1661,10 @@ GROOVE_HD void sampler_chunk_loop(const SamplerParams& p, const SampleLoop& lp, 
   }
   if (count) s.idx = sample_loop_pos(c0, (uint64_t)valid * s.step, ls, le); // (no frame: the cursor is not folded either)
   if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+  return valid;
 }
 template <int MODE, int C>
-GROOVE_HD void sampler_chunk_loop_stereo(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) {
+GROOVE_HD uint32_t sampler_chunk_loop_stereo(const SamplerParams& p, const SampleLoop& lp, SamplerState& s, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) { // returns `valid`
   using T = SampleTaps<MODE>;
   const bool loops = sampler_voice_loops(p, s, lp);
   const uint32_t ls = loops ? lp.start : 0u, le = loops ? lp.end : 0u;
@@ -1698,6 +1699,94 @@ GROOVE_HD void sampler_chunk_loop_stereo(const SamplerParams& p, const SampleLoo
   }
   if (count) s.idx = sample_loop_pos(c0, (uint64_t)valid * s.step, ls, le); // (no frame: the cursor is not folded either)
   if (s.playing && valid < count) s.playing = 0; // ran off the end inside the chunk
+  return valid;
+}
+
+// AMPLITUDE ENVELOPES (groove_bank_set_sample_envelopes; docs/DSP_SPEC.md section 7): a bank property like the loops.  A sample may
+// carry one envelope (section 3's shape and stage rules: EnvParams / EnvState above).  A voice is ENVELOPED when its sample has one and
+// the voice is no one-shot; every other voice plays sampler_frame_loop, bit for bit.  The records live in a buffer of their own, word-
+// major [13][n]: a voice's EnvParams (6 words) and EnvState (7 words).  A voice without an envelope carries release_len < 0 there (a
+// time is never negative), so the kernels ask the record and nothing else.
+constexpr uint32_t kSampleEnvParamWords = 6, kSampleEnvStateWords = 7, kSampleEnvWords = kSampleEnvParamWords + kSampleEnvStateWords;
+static_assert(sizeof(EnvParams) == 4 * kSampleEnvParamWords && sizeof(EnvState) == 4 * kSampleEnvStateWords, "the envelope buffer's rows are the two records' words");
+GROOVE_HD EnvParams sample_env_none() { return EnvParams{0.0f, 0u, 0.0f, 0u, 0.0f, -1.0f}; }
+GROOVE_HD bool sampler_voice_enveloped(const SamplerParams& p, const EnvParams& ep) { return ep.release_len >= 0.0f && !p.one_shot; }
+// The per-frame DEFINITION, mono and stereo, every mode; every other form equals it bit for bit.  Note-off released the envelope and
+// left `playing` alone (derive.h sampler_note_env): the voice plays, and loops, until its release has ended.
+template <int MODE>
+GROOVE_HD float sampler_frame_env(const SamplerParams& p, const SampleLoop& lp, const EnvParams& ep, SamplerState& s, EnvState& es, const float* bank) {
+  if (!sampler_voice_enveloped(p, ep)) return sampler_frame_loop<MODE>(p, lp, s, bank);
+  if (!s.playing) return 0.0f;
+  env_tick(es, ep);
+  if (es.state == ENV_IDLE) { s.playing = 0; return 0.0f; } // the release has ended; the cursor stays where it is
+  const float v = sampler_frame_loop<MODE>(p, lp, s, bank);
+  if (!s.playing) { env_init(es); return 0.0f; } // ran off the sample's end
+  return v * es.value;
+}
+template <int MODE>
+GROOVE_HD void sampler_frame_env_stereo(const SamplerParams& p, const SampleLoop& lp, const EnvParams& ep, SamplerState& s, EnvState& es, const SamplePair* bank, float& L, float& R) {
+  if (!sampler_voice_enveloped(p, ep)) { sampler_frame_loop_stereo<MODE>(p, lp, s, bank, L, R); return; }
+  L = R = 0.0f;
+  if (!s.playing) return;
+  env_tick(es, ep);
+  if (es.state == ENV_IDLE) { s.playing = 0; return; }
+  float l, r;
+  sampler_frame_loop_stereo<MODE>(p, lp, s, bank, l, r);
+  if (!s.playing) { env_init(es); return; }
+  L = l * es.value;
+  R = r * es.value;
+}
+// The envelope's share of a chunk of `count` frames of an enveloped voice that plays: e[k] the factor of frame k for k < live, `live`
+// (returned) the frames before the one whose tick finds the envelope idle, and `es` after min(count, live + 1) ticks.
+template <int C>
+GROOVE_HD uint32_t sampler_env_chunk(const EnvParams& ep, EnvState& es, uint32_t count, float (&e)[C]) {
+  uint32_t live = 0;
+  bool going = true;
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    e[k] = 0.0f;
+    if (going && (uint32_t)k < count) {
+      env_tick(es, ep);
+      if (es.state == ENV_IDLE) going = false;
+      else { e[k] = es.value; live = (uint32_t)k + 1u; }
+    }
+  }
+  return live;
+}
+// After a chunk: `live` and the ticked envelope `t` from sampler_env_chunk, `valid` the frames that played (sampler_chunk_loop on
+// `live` frames, which has stopped a voice that ran off its sample).  The sample's end and the envelope's on the same frame: the
+// definition ticks first, so the voice stops with its envelope idle, not initialised.
+GROOVE_HD void sampler_env_chunk_end(SamplerState& s, EnvState& es, const EnvState& t, uint32_t valid, uint32_t live, uint32_t count) {
+  if (valid < live) { env_init(es); return; } // ran off the end: frame `valid` ticked, found the end and initialised the envelope
+  es = t;
+  if (live < count) s.playing = 0; // idle at frame `live`
+}
+// sampler_chunk_loop / _stereo with the envelope: the chunk's C * N fetches in flight as there, min(valid, frames until idle) frames
+// play, one fp32 multiply per frame and channel.
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_env(const SamplerParams& p, const SampleLoop& lp, const EnvParams& ep, SamplerState& s, EnvState& es, const float* bank, uint32_t count, float (&v)[C]) {
+  if (!sampler_voice_enveloped(p, ep) || !s.playing) { (void)sampler_chunk_loop<MODE, C>(p, lp, s, bank, count, v); return; }
+  float e[C];
+  EnvState t = es;
+  const uint32_t live = sampler_env_chunk<C>(ep, t, count, e);
+  const uint32_t valid = sampler_chunk_loop<MODE, C>(p, lp, s, bank, live, v);
+#pragma unroll
+  for (int k = 0; k < C; ++k) v[k] = (uint32_t)k < valid ? v[k] * e[k] : 0.0f;
+  sampler_env_chunk_end(s, es, t, valid, live, count);
+}
+template <int MODE, int C>
+GROOVE_HD void sampler_chunk_env_stereo(const SamplerParams& p, const SampleLoop& lp, const EnvParams& ep, SamplerState& s, EnvState& es, const SamplePair* bank, uint32_t count, float (&l)[C], float (&r)[C]) {
+  if (!sampler_voice_enveloped(p, ep) || !s.playing) { (void)sampler_chunk_loop_stereo<MODE, C>(p, lp, s, bank, count, l, r); return; }
+  float e[C];
+  EnvState t = es;
+  const uint32_t live = sampler_env_chunk<C>(ep, t, count, e);
+  const uint32_t valid = sampler_chunk_loop_stereo<MODE, C>(p, lp, s, bank, live, l, r);
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    l[k] = (uint32_t)k < valid ? l[k] * e[k] : 0.0f;
+    r[k] = (uint32_t)k < valid ? r[k] * e[k] : 0.0f;
+  }
+  sampler_env_chunk_end(s, es, t, valid, live, count);
 }
 
 // ------------------------------------------------------------------ effects (a8, a9)

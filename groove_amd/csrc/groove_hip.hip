@@ -132,6 +132,14 @@ struct groove_bank {
   std::vector<groove_sample_loop> loops;
   bool looped = false;
   uint32_t* d_loops = nullptr;
+  // sampler bank: the samples' amplitude envelopes (groove_bank_set_sample_envelopes; empty: none) and which samples have one, whether
+  // any has (picks the kernels' ENV instantiations, which are built on the LOOP text: d_loops is then allocated too, zeros for no loop)
+  // and, allocated by the first setter call, each VOICE's EnvParams and EnvState words [13][n] (dsp_core.h kSampleEnvWords)
+  std::vector<groove_envelope_params> envs;
+  std::vector<uint32_t> env_enabled;
+  bool enveloped = false;
+  uint32_t* d_env = nullptr;
+  std::string form_text; // groove_bank_kernel_form's answer for an enveloped bank (the others are literals)
   // welsh: the bank links' per-lane shadow [CTL_DCA_WORDS][n] of dca gain and pan (internal lane order; ctl_link.h), allocated with the first
   // gain or pan link onto the bank and refreshed by welsh_upload_params from then on; and how many live links reach the filter cutoff
   // (welsh_plan.h welsh_flag_filter_f32: no WF_FILTER_F32 while there is one).  fm: the same owner with CTL_FM_WORDS rows — gain, pan, depth,
@@ -627,6 +635,25 @@ int fm_upload_params(groove_bank* b) {
   return b->d_dca ? fm_upload_shadow(b) : 0;
 }
 int sampler_upload_params(groove_bank* b) { return upload_soa(b->ctx, b->d_params, sampler_derive_params(b)); }
+// An enveloped sampler bank's records [13][n] from the kept groove_envelope_params: the parameters derived at the ctx's rate and spread
+// over the voices by sample_index (release_len < 0 for a voice whose sample has none), every envelope idle.
+int sampler_upload_envelopes(groove_bank* b) {
+  groove_ctx* ctx = b->ctx;
+  const uint32_t n = b->n;
+  std::vector<uint32_t> w((size_t)kSampleEnvWords * n);
+  EnvState idle;
+  env_init(idle);
+  for (uint32_t v = 0; v < n; ++v) {
+    const uint32_t i = b->sampler[v].sample_index;
+    const EnvParams ep = i < b->envs.size() && b->env_enabled[i] ? derive_env(b->envs[i], ctx->sr) : sample_env_none();
+    uint32_t rec[kSampleEnvWords];
+    std::memcpy(rec, &ep, sizeof(ep));
+    std::memcpy(rec + kSampleEnvParamWords, &idle, sizeof(idle));
+    for (uint32_t k = 0; k < kSampleEnvWords; ++k) w[(size_t)k * n + v] = rec[k];
+  }
+  GHIP(ctx, ctx_memcpy(ctx, b->d_env, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
 
 int bank_derive_and_upload(groove_bank* b) {
   groove_ctx* ctx = b->ctx;
@@ -647,6 +674,7 @@ int bank_derive_and_upload(groove_bank* b) {
     std::vector<SamplerState> S(n, SamplerState{0, 0, 0, 0});
     if (sampler_upload_params(b)) return 1;
     if (upload_soa(ctx, b->d_state, S)) return 1;
+    if (b->enveloped && sampler_upload_envelopes(b)) return 1; // re-derived at the new rate, idle like the state
   }
   b->pending.clear();
   return 0;
@@ -677,7 +705,7 @@ int launch_events(groove_bank* b, const groove_note_event* ev, uint32_t count, i
                        b->d_state, b->d_cold, b->n, (double)ctx->sr);
   else
     hipLaunchKernelGGL(sampler_events_kernel, grid, blk, 0, st, ev, count, all_event, b->d_params,
-                       b->d_state, b->n);
+                       b->d_state, b->n, b->enveloped ? b->d_env : (uint32_t*)nullptr);
   GHIP(ctx, hipGetLastError());
   return 0;
 }
@@ -1626,6 +1654,11 @@ int groove_bank_set_sample_loops(groove_bank* b, const groove_sample_loop* loops
     b->loops.assign(loops, loops + n_samples);
   } else {
     b->loops.clear();
+    if (b->d_loops) { // (an enveloped bank's kernels go on reading the table: zeros, no loop)
+      GHIP(ctx, hipSetDevice(ctx->device));
+      GHIP(ctx, ctx_wait(ctx));
+      GHIP(ctx, hipMemsetAsync(b->d_loops, 0, (size_t)2 * b->n * 4, ctx->stream));
+    }
   }
   b->looped = any;
   return 0;
@@ -1639,6 +1672,69 @@ uint32_t groove_bank_sample_loops(groove_bank* b, groove_sample_loop* out, uint3
     looped += l.end != 0;
   }
   return looped;
+}
+// Like the loops a property of the bank beside parameters and state, in a buffer of its own (d_env).  The kernels read a voice's
+// record by its index, so the samples' envelopes are spread over the voices (sampler_upload_envelopes).
+int groove_bank_set_sample_envelopes(groove_bank* b, const groove_envelope_params* env, const uint32_t* enabled, uint32_t n_samples) {
+  if (!b) return fail(nullptr, "groove_bank_set_sample_envelopes: bank is NULL");
+  groove_ctx* ctx = b->ctx;
+  if (b->kind != BANK_SAMPLER) return fail(ctx, "groove_bank_set_sample_envelopes: only sampler and drumkit banks play samples");
+  bool any = false;
+  if (env) {
+    if (n_samples != b->descs.size()) return fail(ctx, "groove_bank_set_sample_envelopes: n_samples is not the bank's sample count (" + std::to_string(b->descs.size()) + ")");
+    for (uint32_t i = 0; i < n_samples; ++i) {
+      if (enabled && !enabled[i]) continue;
+      const groove_envelope_params& e = env[i];
+      if (!(e.attack >= 0.0) || !(e.decay >= 0.0) || !(e.release >= 0.0) || !std::isfinite(e.attack) || !std::isfinite(e.decay) || !std::isfinite(e.release))
+        return fail(ctx, "groove_bank_set_sample_envelopes: a negative or non-finite time (sample " + std::to_string(i) + ")");
+      if (!(e.sustain >= 0.0 && e.sustain <= 1.0)) return fail(ctx, "groove_bank_set_sample_envelopes: sustain outside [0, 1] (sample " + std::to_string(i) + ")");
+      any = true;
+    }
+  }
+  if (flush_events(b)) return 1; // (queued notes come first: they see the envelopes they were sent under)
+  if (ctx_join(ctx)) return 1;
+  b->ctx_touched = true;
+  if (!any && !b->enveloped) { b->envs.clear(); b->env_enabled.clear(); return 0; }
+  GHIP(ctx, hipSetDevice(ctx->device));
+  GHIP(ctx, ctx_wait(ctx)); // (the last launch that read d_env has finished)
+  const uint32_t n = b->n;
+  if (any) {
+    if (!b->d_env && hipMalloc(&b->d_env, (size_t)kSampleEnvWords * n * 4) != hipSuccess) { b->d_env = nullptr; return fail(ctx, "groove_bank_set_sample_envelopes: hipMalloc failed"); }
+    if (!b->d_loops) { // the ENV kernels are the LOOP text: a loop table of zeros for a bank that never had a loop
+      if (hipMalloc(&b->d_loops, (size_t)2 * n * 4) != hipSuccess) { b->d_loops = nullptr; return fail(ctx, "groove_bank_set_sample_envelopes: hipMalloc failed"); }
+      GHIP(ctx, hipMemsetAsync(b->d_loops, 0, (size_t)2 * n * 4, ctx->stream));
+    }
+    b->envs.assign(env, env + n_samples);
+    b->env_enabled.assign(n_samples, 1u);
+    if (enabled) b->env_enabled.assign(enabled, enabled + n_samples);
+    if (sampler_upload_envelopes(b)) return 1;
+  }
+  hipLaunchKernelGGL(sampler_env_setup_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, b->d_params, b->d_state, b->d_env, n, any ? 0 : 1);
+  GHIP(ctx, hipGetLastError());
+  if (!any) { b->envs.clear(); b->env_enabled.clear(); }
+  b->enveloped = any;
+  return 0;
+}
+uint32_t groove_bank_sample_envelopes(groove_bank* b, groove_envelope_params* out, uint32_t* enabled_out, uint32_t cap) {
+  if (!b || b->kind != BANK_SAMPLER) return 0;
+  uint32_t count = 0;
+  for (size_t i = 0; i < b->descs.size(); ++i) {
+    const bool on = i < b->envs.size() && b->env_enabled[i];
+    if (out && i < cap) out[i] = on ? b->envs[i] : groove_envelope_params{};
+    if (enabled_out && i < cap) enabled_out[i] = on ? 1u : 0u;
+    count += on;
+  }
+  return count;
+}
+int groove_bank_download_sample_envelope_state(groove_bank* b, uint32_t* words) {
+  if (!b || !words) return fail(b ? b->ctx : nullptr, "groove_bank_download_sample_envelope_state: NULL argument");
+  groove_ctx* ctx = b->ctx;
+  if (b->kind != BANK_SAMPLER || !b->enveloped) return fail(ctx, "groove_bank_download_sample_envelope_state: the bank has no sample envelopes");
+  if (flush_events(b)) return 1;
+  if (ctx_join(ctx)) return 1;
+  GHIP(ctx, ctx_wait(ctx));
+  GHIP(ctx, ctx_memcpy(ctx, words, b->d_env + (size_t)kSampleEnvParamWords * b->n, (size_t)kSampleEnvStateWords * b->n * 4, hipMemcpyDeviceToHost));
+  return 0;
 }
 int groove_bank_destroy(groove_bank* b) {
   if (!b) return 0;
@@ -1657,7 +1753,7 @@ int groove_bank_destroy(groove_bank* b) {
     if (l->bank == b) l->bank = nullptr;
   (void)hipFree(b->d_dca);
   for (int k = 0; k < 2; ++k) { if (b->h_ev[k]) (void)hipHostFree(b->h_ev[k]); if (b->ev_staged[k]) (void)hipEventDestroy(b->ev_staged[k]); }
-  (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_loops); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
+  (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_cold); (void)hipFree(b->d_pcm); (void)hipFree(b->d_loops); (void)hipFree(b->d_env); (void)hipFree(b->d_ev[0]); (void)hipFree(b->d_ev[1]); (void)hipFree(b->d_waves); (void)hipFree(b->d_wg_list); (void)hipFree(b->d_wg_cls); (void)hipFree(b->d_wg_base); (void)hipFree(b->d_wg_f32);
   delete b;
   return 0;
 }
@@ -1850,19 +1946,22 @@ static void launch_small_uniform(const groove_bank* b, const UniformArgs& a, hip
     launch_welsh_kind(k, r, st, fused, (k == 5 || !p.count[5]) ? done : nullptr);
   }
 }
-// The serial sampler kernel: one mode, with or without looped samples (LOOP: b->d_loops, the voices' loop words).
-extern "C++" template <int MODE, bool LOOP>
+// The serial sampler kernel: one mode, with or without looped samples (LOOP: b->d_loops, the voices' loop words), with or without
+// enveloped ones (ENV, on the LOOP text: b->d_env, the voices' envelope records).
+extern "C++" template <int MODE, bool LOOP, bool ENV = false>
 static void launch_sampler_serial_form(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
   const uint32_t* loops = LOOP ? b->d_loops : nullptr;
+  uint32_t* envs = ENV ? b->d_env : nullptr;
   if (b->pcm_stereo) {
-    if (fused) launch_bound(sampler_render_kernel<true, true, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
-    else launch_bound(sampler_render_kernel<false, true, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
-  } else if (fused) launch_bound(sampler_render_kernel<true, false, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
-  else launch_bound(sampler_render_kernel<false, false, MODE, LOOP>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops);
+    if (fused) launch_bound(sampler_render_kernel<true, true, MODE, LOOP, ENV>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops, envs);
+    else launch_bound(sampler_render_kernel<false, true, MODE, LOOP, ENV>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops, envs);
+  } else if (fused) launch_bound(sampler_render_kernel<true, false, MODE, LOOP, ENV>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops, envs);
+  else launch_bound(sampler_render_kernel<false, false, MODE, LOOP, ENV>, grid, blk, st, done, b->d_params, b->d_state, b->n, frames, chs, out, rows, (const float*)b->d_pcm, loops, envs);
 }
 extern "C++" template <int MODE>
 static void launch_sampler_serial_mode(groove_bank* b, uint32_t frames, bool fused, size_t chs, float* out, float* rows, dim3 grid, dim3 blk, hipStream_t st, hipEvent_t done) {
-  if (b->looped) launch_sampler_serial_form<MODE, true>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+  if (b->enveloped) launch_sampler_serial_form<MODE, true, true>(b, frames, fused, chs, out, rows, grid, blk, st, done);
+  else if (b->looped) launch_sampler_serial_form<MODE, true>(b, frames, fused, chs, out, rows, grid, blk, st, done);
   else launch_sampler_serial_form<MODE, false>(b, frames, fused, chs, out, rows, grid, blk, st, done);
 }
 // Every form but the big uniform one is ONE launch sequence on ONE stream, and this is where it is launched.  fused: `rows` =
@@ -1880,7 +1979,7 @@ static void launch_single(groove_bank* b, Form form, uint32_t frames, bool fused
       if (prev) a.prev = *prev;
       if (head) { a.bq_coef = head->d_coef; a.bq_st = head->d_st; a.bq_wet = head->d_wet; }
       if (b->kind == BANK_FM) { a.vpw = tp_vpw(b); launch_fm_tp(a, st, fused, done); }
-      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->pcm_interp, b->looped ? b->d_loops : nullptr, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
+      else if (b->kind == BANK_SAMPLER) { a.vpw = sampler_vpw; launch_sampler_tp(a, b->d_pcm, b->pcm_stereo, b->pcm_interp, b->looped || b->enveloped ? b->d_loops : nullptr, b->enveloped ? b->d_env : nullptr, b->inline_ev, st, fused, done); b->inline_ev.n = 0; }
       else { a.full_coef = b->plan.tp_full_coef; a.vpw = tp_vpw(b); launch_welsh_tp(a, st, fused, done); }
       break;
     }
@@ -2279,7 +2378,7 @@ int groove_bank_render_mix_deferred(groove_bank* b, uint32_t frames, float* bus_
 // groove_bank_render_mix_deferred for SEVERAL small banks of different kinds at once: ONE launch for the whole block (welsh_tp.h
 // tp_mixed_kernel: a grid whose workgroups dispatch on their index into the Welsh / FM / sampler time-parallel bodies), one row
 // buffer, one carried reduction — Orchestrator::gather_audio's one sum over all instruments (orchestrator.rs:397-410).  Takes
-// projects with at most one time-parallel bank of each kind, no stereo, interpolated or looped sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
+// projects with at most one time-parallel bank of each kind, no stereo, interpolated, looped or enveloped sampler bank, and at most 2,048 rows in all; anything else goes bank by bank
 // through groove_bank_render_mix_deferred, in the order given.
 int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks, uint32_t n_banks, uint32_t frames, float* bus_dev, int accumulate) {
   if (!ctx || !bus_dev || (n_banks && !banks)) return fail(ctx, "groove_banks_render_mix_deferred: NULL argument");
@@ -2296,7 +2395,7 @@ int groove_banks_render_mix_deferred(groove_ctx* ctx, groove_bank* const* banks,
     if (!b) return fail(ctx, "groove_banks_render_mix_deferred: NULL bank");
     if (b->ctx != ctx) return fail(ctx, "groove_banks_render_mix_deferred: a bank of another ctx");
     const int k = b->kind == BANK_WELSH ? 0 : b->kind == BANK_FM ? 1 : 2;
-    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo || b->pcm_interp != GROOVE_SAMPLE_NEAREST || b->looped) ok = false; // (tp_mixed_kernel's sampler body is the mono, nearest, loop-free one)
+    if (of_kind[k] || !use_tp(b, frames) || (k == 0 && b->plan.tp_full_coef) || b->pcm_stereo || b->pcm_interp != GROOVE_SAMPLE_NEAREST || b->looped || b->enveloped) ok = false; // (tp_mixed_kernel's sampler body is the mono, nearest, loop-free one without envelopes)
     of_kind[k] = b;
   }
   TpMixedArgs m{};
@@ -2376,7 +2475,16 @@ int groove_bank_render_mix(groove_bank* b, uint32_t frames, float* bus_dev, int 
   GHIP(ctx, hipGetLastError());
   return 0;
 }
+static const char* kernel_form_text(groove_bank* b, uint32_t frames, int fused);
 const char* groove_bank_kernel_form(groove_bank* b, uint32_t frames, int fused) {
+  const char* text = kernel_form_text(b, frames, fused);
+  if (!b || b->kind != BANK_SAMPLER || !b->enveloped) return text;
+  b->form_text = text; // "... (a, b)" -> "... (a, b, enveloped)"
+  if (!b->form_text.empty() && b->form_text.back() == ')') b->form_text.pop_back();
+  b->form_text += ", enveloped)";
+  return b->form_text.c_str();
+}
+static const char* kernel_form_text(groove_bank* b, uint32_t frames, int fused) {
   if (!b) return "";
   const Form form = form_of(b, frames);
   switch (form) {
@@ -2419,6 +2527,10 @@ int groove_bank_reset(groove_bank* b) {
   else { const SamplerState s{0, 0, 0, 0}; std::memcpy(w.w, &s, sizeof(s)); }
   hipLaunchKernelGGL(state_fill_kernel, dim3(blocks_for(b->n)), dim3(kThreads), 0, ctx->stream, b->d_state, b->n, b->sw, w);
   GHIP(ctx, hipGetLastError());
+  if (b->kind == BANK_SAMPLER && b->enveloped) { // the envelopes stay, every record idle
+    GHIP(ctx, ctx_wait(ctx));
+    if (sampler_upload_envelopes(b)) return 1;
+  }
   // An FM bank with links: its shadow goes back to the host's copy, and the records with it — gl, gr and depth_beta each come from TWO
   // shadow words, so a shadow refreshed alone would pair the host's gain with a pan that the records no longer hold.
   if (b->kind == BANK_FM && b->d_dca) return fm_upload_params(b);

@@ -877,10 +877,14 @@ __global__ __launch_bounds__(kThreads) void fm_render_kernel(
 // the 512 a 256-thread workgroup may use, no scratch (the compiler's resource table), so the chunk stays 16 frames in every instantiation.
 // LOOP (groove_bank_set_sample_loops): a bank with a looped sample.  `loops` holds each voice's SampleLoop, [2][n] like the records
 // (start row, end row; 0, 0 for a voice whose sample has none), and only these instantiations read it: the others are the text they were.
-template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
+// ENV (groove_bank_set_sample_envelopes): a bank with an enveloped sample, built on the LOOP text (a bank without loops passes a loop
+// table of zeros).  `envs` holds each voice's EnvParams and EnvState, [13][n] (dsp_core.h sampler_voice_enveloped: release_len < 0
+// for a voice without one), loaded once per block and stored once; only these instantiations touch it.
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false, bool ENV = false>
 __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n, uint32_t frames,
-    size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank, const uint32_t* __restrict__ loops) {
+    size_t ch_stride, float* __restrict__ out, float* __restrict__ rows, const float* __restrict__ bank, const uint32_t* __restrict__ loops, uint32_t* __restrict__ envs) {
+  static_assert(LOOP || !ENV, "the enveloped instantiations are built on the looped text");
   const uint32_t v0 = blockIdx.x * kThreads + threadIdx.x;
   const bool active = v0 < n;
   const uint32_t v = active ? v0 : n - 1;
@@ -888,6 +892,10 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
   SamplerState s = soa_load<SamplerState>(state, n, v);
   SampleLoop lp{0, 0};
   if constexpr (LOOP) lp = soa_load<SampleLoop>(loops, n, v);
+  EnvParams ep = sample_env_none();
+  EnvState es;
+  env_init(es);
+  if constexpr (ENV) { ep = soa_load<EnvParams>(envs, n, v); es = soa_load<EnvState>(envs + (size_t)kSampleEnvParamWords * n, n, v); }
   // chunks of 16 frames: sixteen fetches in flight instead of one (sampler_chunk); mono duplicated to both channels
   constexpr uint32_t C = 16, K = FusedAcc::kChunk;
   static_assert(C % K == 0, "whole flush periods of the fused epilogue per chunk");
@@ -896,7 +904,10 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     const uint32_t count = min(C, frames - f0);
     float x[C];
     float xr[STEREO ? C : 1]; // (a stereo bank's right channel; a mono voice is duplicated to both channels)
-    if constexpr (LOOP) {
+    if constexpr (ENV) {
+      if constexpr (STEREO) sampler_chunk_env_stereo<MODE, C>(p, lp, ep, s, es, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
+      else sampler_chunk_env<MODE, C>(p, lp, ep, s, es, bank, count, x);
+    } else if constexpr (LOOP) {
       if constexpr (STEREO) sampler_chunk_loop_stereo<MODE, C>(p, lp, s, reinterpret_cast<const SamplePair*>(bank), count, x, xr);
       else sampler_chunk_loop<MODE, C>(p, lp, s, bank, count, x);
     } else if constexpr (MODE != GROOVE_SAMPLE_NEAREST) {
@@ -915,6 +926,7 @@ __global__ __launch_bounds__(kThreads) void sampler_render_kernel(
     }
   }
   if (active) soa_store(state, n, v, s);
+  if constexpr (ENV) { if (active) soa_store(envs + (size_t)kSampleEnvParamWords * n, n, v, es); }
 }
 
 #ifndef GROOVE_WELSH_CLASS_TU // everything below is defined once, in groove_hip.hip
@@ -1012,8 +1024,9 @@ __global__ void fm_events_kernel(const groove_note_event* __restrict__ ev, uint3
   fm_note(p, s, ratio[v], sr, e.key, e.on != 0);
   soa_store(state, n, v, s);
 }
+// envs: the voices' envelope records [13][n] of a bank with enveloped samples (sampler_note_env), or null (sampler_note)
 __global__ void sampler_events_kernel(const groove_note_event* __restrict__ ev, uint32_t n_ev, int all_event,
-                                      const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n) {
+                                      const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t n, uint32_t* __restrict__ envs) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   groove_note_event e;
   uint32_t v;
@@ -1021,8 +1034,33 @@ __global__ void sampler_events_kernel(const groove_note_event* __restrict__ ev, 
   else { if (i >= n_ev) return; e = ev[i]; v = e.voice; if (v >= n) return; }
   const SamplerParams p = soa_load<SamplerParams>(params, n, v);
   SamplerState s = soa_load<SamplerState>(state, n, v);
-  sampler_note(p, s, e.key, e.on != 0);
+  if (envs) {
+    const EnvParams ep = soa_load<EnvParams>(envs, n, v);
+    EnvState es = soa_load<EnvState>(envs + (size_t)kSampleEnvParamWords * n, n, v);
+    sampler_note_env(p, ep, s, es, e.key, e.on != 0);
+    soa_store(envs + (size_t)kSampleEnvParamWords * n, n, v, es);
+  } else {
+    sampler_note(p, s, e.key, e.on != 0);
+  }
   soa_store(state, n, v, s);
+}
+// groove_bank_set_sample_envelopes: the voices' envelope records after the host has uploaded their parameters.  clear == 0: every
+// record idle, but a SUSTAIN plateau at the sustain level for an enveloped voice that plays.  clear != 0 (the envelopes are being
+// taken away): a voice whose envelope is in RELEASE stops, so that it does not play on without one; the records are left.
+__global__ __launch_bounds__(kThreads) void sampler_env_setup_kernel(const uint32_t* __restrict__ params, uint32_t* __restrict__ state, uint32_t* __restrict__ envs, uint32_t n, int clear) {
+  const uint32_t v = blockIdx.x * kThreads + threadIdx.x;
+  if (v >= n) return;
+  const SamplerParams p = soa_load<SamplerParams>(params, n, v);
+  SamplerState s = soa_load<SamplerState>(state, n, v);
+  const EnvParams ep = soa_load<EnvParams>(envs, n, v);
+  EnvState es = soa_load<EnvState>(envs + (size_t)kSampleEnvParamWords * n, n, v);
+  if (clear) {
+    if (sampler_voice_enveloped(p, ep) && s.playing && es.state == ENV_RELEASE) { s.playing = 0; soa_store(state, n, v, s); }
+    return;
+  }
+  env_init(es);
+  if (sampler_voice_enveloped(p, ep) && s.playing) { env_plateau(es, ENV_SUSTAIN, ep.sustain); es.value = ep.sustain; }
+  soa_store(envs + (size_t)kSampleEnvParamWords * n, n, v, es);
 }
 // ------------------------------------------------------------------ mix bus (a15)
 // Stage 1: grid (segments, rows) with rows = 2*frames; each workgroup sums one segment of

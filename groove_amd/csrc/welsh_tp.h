@@ -59,6 +59,29 @@ GROOVE_HD uint32_t env_idle_at(EnvState s, const EnvParams& p, uint32_t frames) 
   }
   return frames;
 }
+// A sampler voice's amplitude envelope (dsp_core.h sampler_frame_env) in closed form, as the time-parallel sampler body evaluates it:
+// lanes are frames.  `es` is the voice's envelope at the block's first frame, `valid_sample` the frames the cursor alone lets it play.
+// Frames the voice plays: those before the sample's end and before the frame whose tick finds the envelope idle.
+GROOVE_HD uint32_t sampler_env_valid(const EnvState& es, const EnvParams& ep, uint32_t valid_sample, uint32_t frames) {
+  const uint32_t idle = env_idle_at(es, ep, frames);
+  return valid_sample < idle ? valid_sample : idle;
+}
+// The factors of frames n0 .. n0 + kTpChunk - 1: a seek to the lane's first frame, then its ticks.
+GROOVE_HD void sampler_env_lane(EnvState es, const EnvParams& ep, uint32_t n0, float (&e)[kTpChunk]) {
+  env_seek(es, ep, n0);
+#pragma unroll
+  for (uint32_t j = 0; j < kTpChunk; ++j) { env_tick(es, ep); e[j] = es.value; }
+}
+// The envelope after the block.  The sample ended first (valid_sample < idle frame): the frame that found the end initialised it.
+// Otherwise min(frames, valid + 1) ticks: a voice that went idle inside the block has ticked once more than it played — the same
+// when the sample's end and the idle frame coincide, the definition ticks before it looks at the cursor.  `value` is the last tick's.
+GROOVE_HD void sampler_env_block_end(EnvState& es, const EnvParams& ep, uint32_t valid_sample, uint32_t frames) {
+  const uint32_t idle = env_idle_at(es, ep, frames);
+  if (valid_sample < idle) { env_init(es); return; }
+  const uint32_t ticks = idle < frames ? idle + 1u : frames;
+  env_seek(es, ep, ticks);
+  if (ticks) es.value = env_last_value_of(es);
+}
 
 // ------------------------------------------------------------------ the filter as an affine map
 // Phi's columns (the section-1 state never sees section 2, so columns 2 and 3 have only their lower halves)
@@ -880,9 +903,15 @@ template <int WAVES> struct SamplerTpSmem<WAVES, true> { // a stereo bank: the l
 // block's note events; its `valid` is the whole block, frame f is read at the closed form F(idx + f * step) (dsp_core.h
 // sample_loop_advance: a 32-bit modulo on the frame number, the 64-bit sum never formed) and the state it stores is F(idx + frames * step).
 // Whether a voice loops is wave-uniform in the gather (one voice at a time): the fold is a uniform branch.
-template <bool FUSED, int WAVES, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
+// ENV (groove_bank_set_sample_envelopes): a bank with an enveloped sample, built on the LOOP text (a bank without loops passes a loop
+// table of zeros); `envs` = each voice's EnvParams and EnvState, [13][n], read and written by these instantiations only.  The block's
+// note events apply sampler_note_env.  Lane-parallel (lane = voice): `valid` = min(the cursor's, env_idle_at); in the gather one voice's
+// record is broadcast at a time, every lane seeks to its own first frame and ticks its kTpChunk frames (sampler_env_lane), one multiply
+// per frame and channel; the record stored is sampler_env_block_end's.
+template <bool FUSED, int WAVES, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false, bool ENV = false>
 __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __restrict__ bank, const InlineEvents& ie, const uint32_t vpw, const TpWg g, SamplerTpSmem<WAVES, STEREO>& sm,
-                                                const uint32_t* __restrict__ loops = nullptr) {
+                                                const uint32_t* __restrict__ loops = nullptr, uint32_t* __restrict__ envs = nullptr) {
+  static_assert(LOOP || !ENV, "the enveloped instantiations are built on the looped text");
   float (&s_tile)[WAVES][kTpMaxFrames] = sm.tile;
   volatile uint32_t (&s_ev)[WAVES][64] = sm.ev;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -894,6 +923,10 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
   const uint32_t v = mine ? v_begin + lane : (n - 1);
   const SamplerParams p = soa_load<SamplerParams>(a.params, n, v);
   SamplerState s0 = soa_load<SamplerState>(a.state, n, v);
+  EnvParams ep = sample_env_none(); // ENV: this lane's voice's envelope record
+  EnvState es0;
+  env_init(es0);
+  if constexpr (ENV) { ep = soa_load<EnvParams>(envs, n, v); es0 = soa_load<EnvState>(envs + (size_t)kSampleEnvParamWords * n, n, v); }
   if constexpr (FUSED) tp_reduce_prev(a.prev, threadIdx.x, g.pwg, g.pn_wg);
   if (ie.n && cnt) { // this block's note events (strictly increasing voices): those of this wave's voice range
     uint32_t lo = 0, hi = ie.n;
@@ -908,7 +941,8 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     }
     __builtin_amdgcn_wave_barrier(); // (scheduling fence; a wave's LDS operations complete in issue order)
     const uint32_t got = s_ev[wave][lane];
-    if (mine && (got & 0x10000u)) sampler_note(p, s0, got & 0xFFu, (got >> 8) & 1u);
+    if constexpr (ENV) { if (mine && (got & 0x10000u)) sampler_note_env(p, ep, s0, es0, got & 0xFFu, (got >> 8) & 1u); }
+    else if (mine && (got & 0x10000u)) sampler_note(p, s0, got & 0xFFu, (got >> 8) & 1u);
   }
   uint32_t lp_start = 0, lp_end = 0; // this lane's voice loops: its loop (end != 0) and s0.idx folded; otherwise 0, 0
   if constexpr (LOOP) {
@@ -925,6 +959,12 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
       const uint64_t fmax = s0.step ? room / s0.step : (uint64_t)frames;
       valid = fmax >= frames ? frames : (uint32_t)fmax + 1u;
     }
+  }
+  const uint32_t valid_sample = valid; // ENV: what the cursor alone allows; `valid` is cut at the frame that finds the envelope idle
+  uint32_t env_on = 0;                 // ENV: this lane's voice is enveloped and plays
+  if constexpr (ENV) {
+    env_on = mine && s0.playing && sampler_voice_enveloped(p, ep) ? 1u : 0u;
+    if (env_on) valid = sampler_env_valid(es0, ep, valid_sample, frames);
   }
   const uint32_t n0 = lane * kTpChunk;
   float acc[kTpChunk];
@@ -945,6 +985,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     float gain[U];
     uint64_t idx[U], step[U];
     uint32_t ls[LOOP ? U : 1], le[LOOP ? U : 1]; // a looping voice's loop; le == 0: the voice does not loop
+    uint32_t vv[ENV ? U : 1];                    // ENV: the voice's `valid`
     uint32_t any = 0;
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
@@ -956,6 +997,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
       step[u] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)step_hi, k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)step_lo, k);
       playing[u] = k0 + u < cnt ? (uint32_t)__builtin_amdgcn_readlane((int)s0.playing, k) : 0u;
       if constexpr (LOOP) { ls[u] = (uint32_t)__builtin_amdgcn_readlane((int)lp_start, k); le[u] = (uint32_t)__builtin_amdgcn_readlane((int)lp_end, k); }
+      if constexpr (ENV) vv[u] = (uint32_t)__builtin_amdgcn_readlane((int)valid, k);
       any |= playing[u];
     }
     if (!any) continue; // (uniform)
@@ -973,6 +1015,7 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
         if constexpr (LOOP) pos = sample_loop_pos(idx[u], (uint64_t)f * step[u], ls[u], le[u]);
         const uint32_t i = (uint32_t)(pos >> 44);
         ok[u][j] = playing[u] && f < frames && i < len[u];
+        if constexpr (ENV) ok[u][j] = ok[u][j] && f < vv[ENV ? u : 0];
         if constexpr (INTERP) {
           const uint32_t ic = i < len[u] ? i : len[u] - 1;
 #pragma unroll
@@ -1000,6 +1043,19 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
       if (!playing[u]) continue;
       float x[kTpChunk];
       float x_r[STEREO ? kTpChunk : 1];
+      float e[ENV ? kTpChunk : 1]; // ENV: this lane's frames' factors of an enveloped voice (`on`, wave-uniform)
+      bool on = false;
+      if constexpr (ENV) {
+        const int k = (int)min(k0 + u, cnt - 1);
+        on = __builtin_amdgcn_readlane((int)env_on, k) != 0;
+        if (on) { // the voice's record, broadcast; every lane seeks to its own first frame
+          const auto bf = [&](float w) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w), k)); };
+          const auto bu = [&](uint32_t w) { return (uint32_t)__builtin_amdgcn_readlane((int)w, k); };
+          const EnvParams epk{bf(ep.attack_len), bu(ep.attack_N), bf(ep.decay_len), bu(ep.decay_N), bf(ep.sustain), bf(ep.release_len)};
+          const EnvState esk{bu(es0.state), bu(es0.n), bu(es0.N), bf(es0.A), bf(es0.D), bf(es0.inv_len), 0.0f};
+          sampler_env_lane(esk, epk, n0, e);
+        }
+      }
 #pragma unroll
       for (uint32_t j = 0; j < kTpChunk; ++j) {
         if constexpr (INTERP) { // the taps past either end of the sample dropped, then the mode's formula at this frame's fraction
@@ -1018,8 +1074,19 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
             raw_r[u][j] = sample_interp<MODE>(q, t);
           }
         }
+        if constexpr (ENV) { // one more fp32 multiply, after the gain's, for an enveloped voice
+          float xv = raw[u][j] * gain[u];
+          if (on) xv = xv * e[ENV ? j : 0];
+          x[j] = ok[u][j] ? xv : 0.0f; acc[j] += x[j];
+          if constexpr (STEREO) {
+            float xw = raw_r[u][j] * gain[u];
+            if (on) xw = xw * e[ENV ? j : 0];
+            x_r[j] = ok[u][j] ? xw : 0.0f; acc_r[j] += x_r[j];
+          }
+        } else {
         x[j] = ok[u][j] ? raw[u][j] * gain[u] : 0.0f; acc[j] += x[j];
         if constexpr (STEREO) { x_r[j] = ok[u][j] ? raw_r[u][j] * gain[u] : 0.0f; acc_r[j] += x_r[j]; }
+        }
       }
       if (!FUSED) {
         const uint32_t vk = v_begin + k0 + u;
@@ -1066,12 +1133,16 @@ __device__ __forceinline__ void sampler_tp_body(const TpArgs& a, const float* __
     if constexpr (LOOP) s.idx = sample_loop_pos(s0.idx, (uint64_t)valid * s0.step, lp_start, lp_end);
     if (s0.playing && valid < frames) s.playing = 0; // ran off the end inside the block
     soa_store(a.state, n, v, s);
+    if constexpr (ENV) {
+      if (env_on) sampler_env_block_end(es0, ep, valid_sample, frames);
+      soa_store(envs + (size_t)kSampleEnvParamWords * n, n, v, es0);
+    }
   }
 }
-template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false>
-__global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw, const uint32_t* __restrict__ loops) {
+template <bool FUSED, bool STEREO = false, int MODE = GROOVE_SAMPLE_NEAREST, bool LOOP = false, bool ENV = false>
+__global__ __launch_bounds__(kSamplerTpThreads) void sampler_tp_kernel(TpArgs a, const float* __restrict__ bank, InlineEvents ie, uint32_t vpw, const uint32_t* __restrict__ loops, uint32_t* __restrict__ envs) {
   __shared__ SamplerTpSmem<kSamplerTpWaves, STEREO> sm;
-  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO, MODE, LOOP>(a, bank, ie, vpw, tp_wg_own(), sm, loops);
+  sampler_tp_body<FUSED, kSamplerTpWaves, STEREO, MODE, LOOP, ENV>(a, bank, ie, vpw, tp_wg_own(), sm, loops, envs);
 }
 // ------------------------------------------------------------------ several small banks in ONE launch (round 5)
 // A project of a few small banks of different kinds (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096
@@ -1117,7 +1188,7 @@ inline uint32_t mixed_sampler_workgroups(uint32_t n, uint32_t vpw) { const uint3
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done = nullptr); // welsh.vpw 1 | 2, fm.vpw 1 | 4
 void launch_welsh_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.bq_coef set (block-writing form): the BiQuad head fused; done: an event bound to the dispatch
 void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done = nullptr); // a.vpw voices per wavefront (1, 2, 4)
-void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const uint32_t* loops, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames; interpolation: a groove_sample_interpolation; loops: the voices' SampleLoop words [2][n], null for a bank without a looped sample
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const uint32_t* loops, uint32_t* envs, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done = nullptr); // stereo: bank = interleaved L, R frames; interpolation: a groove_sample_interpolation; loops: the voices' SampleLoop words [2][n], null for a bank without a looped sample; envs: the voices' envelope records [13][n] (with loops, zeros for none), null for a bank without an enveloped sample
 inline uint32_t welsh_tp_workgroups(uint32_t n, uint32_t vpw = 1) { return (n + kTpWaves * vpw - 1) / (kTpWaves * vpw); } // FM: groups of 4 vpw voices per workgroup, plain order
 inline uint32_t welsh_tp_grid(uint32_t n, uint32_t vpw = 1) { // Welsh: padded for the XCD-aware mapping (idle workgroups write zero rows)
   const uint32_t g = welsh_tp_workgroups(n, vpw);

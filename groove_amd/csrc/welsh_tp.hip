@@ -42,25 +42,26 @@ void launch_fm_tp(const TpArgs& a, hipStream_t st, bool fused, hipEvent_t done) 
   else if (a.vpw == 2) launch_fm_tp_vpw<2>(a, st, fused, done);
   else launch_fm_tp_vpw<1>(a, st, fused, done);
 }
-template <int MODE, bool LOOP> // one mode, with or without looped samples: the four FUSED x STEREO instantiations
-static void launch_sampler_tp_form(const TpArgs& a, const float* bank, bool stereo, const uint32_t* loops, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done, dim3 grid, dim3 blk, uint32_t vpw) {
+template <int MODE, bool LOOP, bool ENV = false> // one mode, with or without looped samples, with or without envelopes (on the looped text): the four FUSED x STEREO instantiations
+static void launch_sampler_tp_form(const TpArgs& a, const float* bank, bool stereo, const uint32_t* loops, uint32_t* envs, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done, dim3 grid, dim3 blk, uint32_t vpw) {
   if (stereo) {
-    if (fused) launch_bound(sampler_tp_kernel<true, true, MODE, LOOP>, grid, blk, st, done, a, bank, ie, vpw, loops);
-    else launch_bound(sampler_tp_kernel<false, true, MODE, LOOP>, grid, blk, st, done, a, bank, ie, vpw, loops);
-  } else if (fused) launch_bound(sampler_tp_kernel<true, false, MODE, LOOP>, grid, blk, st, done, a, bank, ie, vpw, loops);
-  else launch_bound(sampler_tp_kernel<false, false, MODE, LOOP>, grid, blk, st, done, a, bank, ie, vpw, loops);
+    if (fused) launch_bound(sampler_tp_kernel<true, true, MODE, LOOP, ENV>, grid, blk, st, done, a, bank, ie, vpw, loops, envs);
+    else launch_bound(sampler_tp_kernel<false, true, MODE, LOOP, ENV>, grid, blk, st, done, a, bank, ie, vpw, loops, envs);
+  } else if (fused) launch_bound(sampler_tp_kernel<true, false, MODE, LOOP, ENV>, grid, blk, st, done, a, bank, ie, vpw, loops, envs);
+  else launch_bound(sampler_tp_kernel<false, false, MODE, LOOP, ENV>, grid, blk, st, done, a, bank, ie, vpw, loops, envs);
 }
 template <int MODE>
-static void launch_sampler_tp_mode(const TpArgs& a, const float* bank, bool stereo, const uint32_t* loops, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done, dim3 grid, dim3 blk, uint32_t vpw) {
-  if (loops) launch_sampler_tp_form<MODE, true>(a, bank, stereo, loops, ie, st, fused, done, grid, blk, vpw);
-  else launch_sampler_tp_form<MODE, false>(a, bank, stereo, nullptr, ie, st, fused, done, grid, blk, vpw);
+static void launch_sampler_tp_mode(const TpArgs& a, const float* bank, bool stereo, const uint32_t* loops, uint32_t* envs, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done, dim3 grid, dim3 blk, uint32_t vpw) {
+  if (envs) launch_sampler_tp_form<MODE, true, true>(a, bank, stereo, loops, envs, ie, st, fused, done, grid, blk, vpw);
+  else if (loops) launch_sampler_tp_form<MODE, true>(a, bank, stereo, loops, nullptr, ie, st, fused, done, grid, blk, vpw);
+  else launch_sampler_tp_form<MODE, false>(a, bank, stereo, nullptr, nullptr, ie, st, fused, done, grid, blk, vpw);
 }
-void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const uint32_t* loops, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
+void launch_sampler_tp(const TpArgs& a, const float* bank, bool stereo, uint32_t interpolation, const uint32_t* loops, uint32_t* envs, const InlineEvents& ie, hipStream_t st, bool fused, hipEvent_t done) {
   const uint32_t vpw = a.vpw > 1 ? a.vpw : sampler_tp_vpw(a.n); // (a.vpw: the deferred form's choice)
   const dim3 grid(sampler_tp_workgroups(a.n, vpw)), blk(kSamplerTpThreads);
-  if (interpolation == GROOVE_SAMPLE_LINEAR) launch_sampler_tp_mode<GROOVE_SAMPLE_LINEAR>(a, bank, stereo, loops, ie, st, fused, done, grid, blk, vpw);
-  else if (interpolation == GROOVE_SAMPLE_CUBIC) launch_sampler_tp_mode<GROOVE_SAMPLE_CUBIC>(a, bank, stereo, loops, ie, st, fused, done, grid, blk, vpw);
-  else launch_sampler_tp_mode<GROOVE_SAMPLE_NEAREST>(a, bank, stereo, loops, ie, st, fused, done, grid, blk, vpw);
+  if (interpolation == GROOVE_SAMPLE_LINEAR) launch_sampler_tp_mode<GROOVE_SAMPLE_LINEAR>(a, bank, stereo, loops, envs, ie, st, fused, done, grid, blk, vpw);
+  else if (interpolation == GROOVE_SAMPLE_CUBIC) launch_sampler_tp_mode<GROOVE_SAMPLE_CUBIC>(a, bank, stereo, loops, envs, ie, st, fused, done, grid, blk, vpw);
+  else launch_sampler_tp_mode<GROOVE_SAMPLE_NEAREST>(a, bank, stereo, loops, envs, ie, st, fused, done, grid, blk, vpw);
 }
 void launch_tp_mixed(const TpMixedArgs& m, const InlineEvents& ie, uint32_t grid, hipStream_t st, hipEvent_t done) {
   const dim3 g(grid), blk(kTpThreads);

@@ -439,6 +439,32 @@ class Sampler(Instrument):
         arr = (T.SampleLoop * len(loops))(*[T.SampleLoop(int(s), int(e)) for s, e in loops])
         _lib.check(self.ctx.L.groove_bank_set_sample_loops(self.h, arr, len(loops)), self.ctx.h)
 
+    @property
+    def sample_envelopes(self):
+        """groove_bank_sample_envelopes: one (attack, decay, sustain, release) per sample of the bank, seconds and 0..1; None: no envelope."""
+        n = self.n_samples
+        out, on = (T.EnvelopeParams * n)(), (C.c_uint32 * n)()
+        self.ctx.L.groove_bank_sample_envelopes(self.h, out, on, n)
+        return [(e.attack, e.decay, e.sustain, e.release) if f else None for e, f in zip(out, on)]
+
+    @sample_envelopes.setter
+    def sample_envelopes(self, envelopes):
+        """groove_bank_set_sample_envelopes: one (attack, decay, sustain, release) or None per sample, or None to clear them all; from
+        the next render on, parameters and state stay as they are."""
+        if envelopes is None:
+            _lib.check(self.ctx.L.groove_bank_set_sample_envelopes(self.h, None, None, 0), self.ctx.h)
+            return
+        n = len(envelopes)
+        arr = (T.EnvelopeParams * n)(*[T.EnvelopeParams(*[float(x) for x in (e or (0.0, 0.0, 1.0, 0.0))]) for e in envelopes])
+        on = (C.c_uint32 * n)(*[0 if e is None else 1 for e in envelopes])
+        _lib.check(self.ctx.L.groove_bank_set_sample_envelopes(self.h, arr, on, n), self.ctx.h)
+
+    def sample_envelope_state(self):
+        """groove_bank_download_sample_envelope_state: the voices' envelope state words, [7][n] uint32 (state, n, N, A, D, inv_len, value)."""
+        out = np.empty((7, self.n), dtype=np.uint32)
+        _lib.check(self.ctx.L.groove_bank_download_sample_envelope_state(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx.h)
+        return out
+
 
 class Effect:
     """IsEffect: TransformsAudio per lane over a block."""

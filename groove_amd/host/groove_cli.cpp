@@ -1,7 +1,7 @@
 // groove-cli-hip — offline renderer, the GPU-path counterpart of the reference's `groove-cli`
 // (/root/reference/src/bin/groove-cli.rs:24-53 args, :56-158 main; gated at the reference commit).
 //
-//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--quiet] [--perf] [--debug] FILE...
+//   groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--sample-envelope A,D,S,R] [--quiet] [--perf] [--debug] FILE...
 //
 // --device-filter-links: `controls` onto a filter's cutoff, q or passband-ripple stay on the device (Orchestrator::set_filter_links_on_device),
 // a signal source's among them, which are dropped with a warning otherwise.
@@ -19,6 +19,9 @@
 // (Orchestrator::set_sample_interpolation); nearest, the reference's reading, by default.
 // --sample-loops: a sampler whose WAV file carries a forward sustain loop (`smpl` chunk) repeats it while a note is held
 // (Orchestrator::set_sample_loops); without it a sampler plays its file once.
+// --sample-envelope A,D,S,R: samplers get an amplitude envelope — attack, decay in seconds, sustain 0..1, release in seconds — so a
+// note fades in and has a release tail after its note-off (Orchestrator::set_sample_envelope); without it a sampler voice starts at
+// full level and stops at its note-off.  Drumkits get none.
 //
 // For each project file: SongSettings::new_from_project_file → instantiate → update_sample_rate(44100)
 // → run_performance(buffer) → (with --wav) send_performance_to_file(<input with .json5/.json → .wav>).
@@ -44,6 +47,8 @@ int main(int argc, char** argv) {
   bool wav = false, quiet = false, perf = false, debug = false, synthetic = false, filter_links = false, device_trips = false, instrument_controls = false, wet_links = false, wet_run = false, stereo_samples = false, sample_loops = false;
   int device = 0;
   uint32_t sample_interpolation = GROOVE_SAMPLE_NEAREST;
+  bool sample_envelope_on = false;
+  groove_envelope_params sample_envelope{};
   std::string assets = "assets";
   std::vector<std::string> inputs;
   for (int i = 1; i < argc; ++i) {
@@ -60,6 +65,13 @@ int main(int argc, char** argv) {
     else if (a == "--wet-reverb-run") wet_run = true;
     else if (a == "--stereo-samples") stereo_samples = true;
     else if (a == "--sample-loops") sample_loops = true;
+    else if (a == "--sample-envelope" && i + 1 < argc) {
+      char extra = 0;
+      if (std::sscanf(argv[++i], "%lf,%lf,%lf,%lf%c", &sample_envelope.attack, &sample_envelope.decay, &sample_envelope.sustain, &sample_envelope.release, &extra) != 4) {
+        std::fprintf(stderr, "--sample-envelope takes four numbers A,D,S,R (seconds, seconds, 0..1, seconds), got '%s'\n", argv[i]); return 2;
+      }
+      sample_envelope_on = true;
+    }
     else if (a == "--sample-interpolation" && i + 1 < argc) {
       const std::string m = argv[++i];
       if (m == "nearest") sample_interpolation = GROOVE_SAMPLE_NEAREST;
@@ -71,7 +83,7 @@ int main(int argc, char** argv) {
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--version" || a == "-v") { std::printf("groove-cli-hip 0.1 (MI355X render path)\n"); return 0; }
     else if (a == "--help" || a == "-h") {
-      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--quiet] [--perf] [--debug] FILE...\n");
+      std::printf("usage: groove-cli-hip [--wav] [--assets DIR] [--device N] [--synthetic-kit] [--device-filter-links] [--device-trips] [--device-instrument-controls] [--device-wet-links] [--wet-reverb-run] [--stereo-samples] [--sample-interpolation nearest|linear|cubic] [--sample-loops] [--sample-envelope A,D,S,R] [--quiet] [--perf] [--debug] FILE...\n");
       return 0;
     } else inputs.push_back(a);
   }
@@ -94,6 +106,7 @@ int main(int argc, char** argv) {
     o.set_wet_links_on_device(wet_links);
     o.set_stereo_samples(stereo_samples);
     o.set_sample_loops(sample_loops);
+    if (sample_envelope_on && o.set_sample_envelope(&sample_envelope)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (o.set_sample_interpolation(sample_interpolation)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (o.set_wet_reverb_run(wet_run)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }
     if (instantiate(o, desc, assets, synthetic)) { std::fprintf(stderr, "%s: %s\n", in.c_str(), o.last_error().c_str()); return 1; }

@@ -514,6 +514,16 @@ int Orchestrator::set_sample_interpolation(uint32_t mode) {
   sample_interpolation_ = mode;
   return 0;
 }
+int Orchestrator::set_sample_envelope(const groove_envelope_params* env) {
+  if (!env) { sample_envelope_on_ = false; return 0; }
+  const double t[3] = {env->attack, env->decay, env->release};
+  for (double x : t)
+    if (!(x >= 0.0) || !std::isfinite(x)) return fail("set_sample_envelope: a negative or non-finite time");
+  if (!(env->sustain >= 0.0 && env->sustain <= 1.0)) return fail("set_sample_envelope: sustain outside [0, 1]");
+  sample_envelope_ = *env;
+  sample_envelope_on_ = true;
+  return 0;
+}
 int Orchestrator::control_link(groove_ctl_link* link, uint64_t at, bool trip_units, bool on_instrument) {
   if (deferring_ && !on_instrument) { deferred_.push_back({0, 0, 0.0, link, at, trip_units}); return 0; }
   if (trip_units ? groove_ctl_trip_apply(link, at) : groove_ctl_link_apply(link, at)) return fail(groove_last_error(ctx_));
@@ -793,7 +803,12 @@ static int add_sampler(void* h, bool stereo, const char* who, const float* pcm, 
   if (stereo ? groove_sampler_create_stereo(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)
              : groove_sampler_create(o->ctx(), pcm, frames, &d, 1, p.data(), voices, &b)) { o->fail(groove_last_error(o->ctx())); return -1; }
   if (apply_sample_interpolation(o, b)) return -1;
-  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::SAMPLER, voices, true, 0.0, false)));
+  double release = 0.0; // Orchestrator::set_sample_envelope: the sample's envelope, and a voice in its tail is busy
+  if (const groove_envelope_params* env = o->sample_envelope()) {
+    if (groove_bank_set_sample_envelopes(b, env, nullptr, 1)) { o->fail(groove_last_error(o->ctx())); groove_bank_destroy(b); return -1; }
+    release = env->release;
+  }
+  return (int)o->add(std::unique_ptr<Entity>(new VoiceBankInstrument(o->ctx(), b, BankControls::SAMPLER, voices, true, release, false)));
 }
 int gh_add_sampler(void* h, const float* pcm, uint64_t frames, double root_hz, uint32_t voices) { return add_sampler(h, false, "gh_add_sampler", pcm, frames, root_hz, voices); }
 int gh_add_sampler_stereo(void* h, const float* pcm_lr, uint64_t frames, double root_hz, uint32_t voices) { return add_sampler(h, true, "gh_add_sampler_stereo", pcm_lr, frames, root_hz, voices); }
@@ -839,6 +854,13 @@ void gh_set_wet_links_on_device(void* h, int on) { ((Orchestrator*)h)->set_wet_l
 int gh_wet_links_on_device(void* h) { return ((Orchestrator*)h)->wet_links_on_device() ? 1 : 0; }
 void gh_set_stereo_samples(void* h, int on) { ((Orchestrator*)h)->set_stereo_samples(on != 0); }
 int gh_stereo_samples(void* h) { return ((Orchestrator*)h)->stereo_samples() ? 1 : 0; }
+int gh_set_sample_envelope(void* h, const groove_envelope_params* env) { return ((Orchestrator*)h)->set_sample_envelope(env); }
+// The envelope samplers are created with: 1 and *out, or 0 when there is none.
+int gh_sample_envelope(void* h, groove_envelope_params* out) {
+  const groove_envelope_params* e = ((Orchestrator*)h)->sample_envelope();
+  if (e && out) *out = *e;
+  return e ? 1 : 0;
+}
 void gh_set_sample_loops(void* h, int on) { ((Orchestrator*)h)->set_sample_loops(on != 0); }
 int gh_sample_loops(void* h) { return ((Orchestrator*)h)->sample_loops() ? 1 : 0; }
 // The forward loop [start, end) of the one sample of a sampler added by gh_add_sampler / gh_add_sampler_stereo (0, 0: none).

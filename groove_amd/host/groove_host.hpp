@@ -486,6 +486,13 @@ class Orchestrator {
   // Off by default: a sampler plays its file once, as the reference does.
   void set_sample_loops(bool on) { sample_loops_ = on; }
   bool sample_loops() const { return sample_loops_; }
+  // A `sampler` created from here on gets this amplitude envelope on its sample (groove_bank_set_sample_envelopes: an attack, and a
+  // release tail after note-off) and is busy until note-off + the envelope's release, the rule Welsh and FM synths follow: the next
+  // note takes another voice while the tail sounds.  Drumkits never do: their voices are one-shots.  NULL: none, the default — a
+  // sampler voice starts at full level and stops at its note-off, as the reference's does.  A negative or non-finite time or a sustain
+  // outside [0, 1] is refused (last_error) and changes nothing.
+  int set_sample_envelope(const groove_envelope_params* env);
+  const groove_envelope_params* sample_envelope() const { return sample_envelope_on_ ? &sample_envelope_ : nullptr; }
   uint64_t sequencing_frame() const { return sequencing_frame_; } // first frame of the block whose controllers are being worked
   uint64_t clock_frames() const { return frames_; }
   uint64_t performance_frames() const; // ceil(end of the last controller)
@@ -534,6 +541,8 @@ class Orchestrator {
   bool instrument_controls_on_device_ = false;
   bool stereo_samples_ = false;
   bool sample_loops_ = false;
+  bool sample_envelope_on_ = false;
+  groove_envelope_params sample_envelope_{};
   uint32_t sample_interpolation_ = GROOVE_SAMPLE_NEAREST;
   void place_trips(); // skip_to_start: which trips are device-resident for this performance
   bool ahead_primed_ = false;   // the current block's instruments were rendered by the previous tick_ahead

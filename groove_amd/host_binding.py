@@ -28,6 +28,7 @@ def load():
         "gh_add_sampler": (i, [vp, _fp, C.c_uint64, d, u32]), "gh_add_sampler_stereo": (i, [vp, _fp, C.c_uint64, d, u32]),
         "gh_set_stereo_samples": (None, [vp, i]), "gh_stereo_samples": (i, [vp]),
         "gh_set_sample_interpolation": (i, [vp, u32]), "gh_sample_interpolation": (u32, [vp]),
+        "gh_set_sample_envelope": (i, [vp, C.POINTER(T.EnvelopeParams)]), "gh_sample_envelope": (i, [vp, C.POINTER(T.EnvelopeParams)]),
         "gh_set_sample_loops": (None, [vp, i]), "gh_sample_loops": (i, [vp]), "gh_set_sample_loop": (i, [vp, i, u32, u32]),
         "gh_read_wav_loop": (i, [C.c_char_p, C.POINTER(u32), C.POINTER(u32)]),
         "gh_add_effect": (i, [vp, u32, C.POINTER(T.FxParams)]),
@@ -120,6 +121,17 @@ class Orchestrator:
         self.L.gh_set_sample_loops(self.h, int(bool(on)))
 
     def sample_loops(self): return bool(self.L.gh_sample_loops(self.h))
+
+    def set_sample_envelope(self, envelope):
+        """A `sampler` created from here on gets the amplitude envelope (attack, decay, sustain, release) — seconds, seconds, 0..1,
+        seconds — on its sample and keeps a voice busy through its release tail; None: none (the default)."""
+        env = None if envelope is None else C.byref(T.EnvelopeParams(*[float(x) for x in envelope]))
+        if self.L.gh_set_sample_envelope(self.h, env):
+            raise RuntimeError(self.L.gh_last_error(self.h).decode())
+
+    def sample_envelope(self):
+        out = T.EnvelopeParams()
+        return (out.attack, out.decay, out.sustain, out.release) if self.L.gh_sample_envelope(self.h, C.byref(out)) else None
 
     def set_sample_loop(self, uid, start, end):
         """The forward loop [start, end), in frames, of the sampler `uid` (add_sampler's return); 0, 0 clears it."""

@@ -69,6 +69,9 @@ SYMBOLS = {
     "groove_bank_sample_interpolation": (_u32, [_vp]),
     "groove_bank_set_sample_loops": (_i, [_vp, C.POINTER(T.SampleLoop), _u32]),
     "groove_bank_sample_loops": (_u32, [_vp, C.POINTER(T.SampleLoop), _u32]),
+    "groove_bank_set_sample_envelopes": (_i, [_vp, C.POINTER(T.EnvelopeParams), C.POINTER(_u32), _u32]),
+    "groove_bank_sample_envelopes": (_u32, [_vp, C.POINTER(T.EnvelopeParams), C.POINTER(_u32), _u32]),
+    "groove_bank_download_sample_envelope_state": (_i, [_vp, C.POINTER(_u32)]),
     "groove_bank_destroy": (_i, [_vp]),
     "groove_bank_voices": (_u32, [_vp]),
     "groove_bank_note_events": (_i, [_vp, C.POINTER(T.NoteEvent), _u32]),

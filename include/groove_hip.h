@@ -202,7 +202,8 @@ uint32_t groove_bank_sample_interpolation(groove_bank* bank);
  * n_samples the bank's sample count; loops == NULL clears every loop.  A voice loops while its sample has a loop, it is no one_shot
  * voice (a drumkit voice ignores note-off and would never end) and it plays: its Q20.44 cursor is folded into [0, end) — F(x) = x
  * below end << 44, start + (x - start) mod (end - start) from there on, exact 64-bit integers, for every length the create calls
- * accept — so the end rule is never met and note-off stops it at the next block start as it stops any sampler voice (no release tail).
+ * accept — so the end rule is never met and note-off stops it at the next block start as it stops any sampler voice (a release tail:
+ * groove_bank_set_sample_envelopes).
  * The split of a render into blocks changes no bit of output or state.  Interpolation taps at or past `end` are read as the loop
  * repeats, taps before the sample's first frame are silence; no tap of a looping voice lies outside [0, end).  Every other voice —
  * on a sample without a loop, or a one_shot voice on a looped one — plays what it played before, bit for bit.  Like the interpolation
@@ -214,6 +215,28 @@ uint32_t groove_bank_sample_interpolation(groove_bank* bank);
  * and returns the number of looped samples; 0 for a bank of another kind. */
 int groove_bank_set_sample_loops(groove_bank* bank, const groove_sample_loop* loops, uint32_t n_samples);
 uint32_t groove_bank_sample_loops(groove_bank* bank, groove_sample_loop* out, uint32_t cap);
+/* AMPLITUDE ENVELOPES: a note gets an attack and a release tail (docs/DSP_SPEC.md section 7).  env[i] is the envelope of the bank's
+ * i-th sample (times in seconds, sustain 0..1; the shape and stage rules are section 3's, the Welsh and FM voices'), n_samples the
+ * bank's sample count; enabled[i] == 0 leaves sample i without one (enabled == NULL: every sample has one); env == NULL clears all.
+ * A voice is ENVELOPED when its sample has an envelope and it is no one_shot voice; every other voice plays what it played before,
+ * bit for bit.  For an enveloped voice note-on starts the sample and attacks (a retrigger from the envelope's current value),
+ * note-off releases and leaves the cursor running — a looping voice loops through its release — and each frame is the plain frame
+ * times the envelope's value, one fp32 multiply; the voice stops on the frame whose tick finds the envelope idle, or at the sample's
+ * end.  The split of a render into blocks changes no bit of output or state, and the gate envelope (0, 0, 1, 0) plays the bank's
+ * bits without envelopes.  SamplerParams, SamplerState and groove_bank_state_words do not change: the envelope records live in a
+ * buffer of their own, allocated by the first call and freed with the bank.  The setter joins the bank's earlier work first, like
+ * groove_bank_set_sample_loops, and may be called between any two renders: every record becomes idle, that of a voice that plays a
+ * SUSTAIN plateau at its sustain level; on clearing, a voice whose envelope is in its release stops (it would play on without one)
+ * and a held voice plays on.  A property of the bank: kept by groove_bank_set_param and gain links, by groove_bank_reset (every
+ * record idle) and by a sample-rate change (parameters derived again, records idle like the state).  Refused with a message for a
+ * bank of another kind, n_samples other than the bank's sample count, a negative or non-finite time, a sustain outside [0, 1].
+ * groove_bank_kernel_form says ", enveloped" while a sample of the bank has an envelope.  The getter writes the first
+ * min(cap, sample count) envelopes and flags (either may be NULL) and returns the number of enveloped samples; 0 for a bank of
+ * another kind.  groove_bank_download_sample_envelope_state copies the voices' envelope state words, [7][n] word-major (state, n, N,
+ * A, D, inv_len, value), for tests and hosts that checkpoint; refused on a bank without envelopes. */
+int groove_bank_set_sample_envelopes(groove_bank* bank, const groove_envelope_params* env, const uint32_t* enabled, uint32_t n_samples);
+uint32_t groove_bank_sample_envelopes(groove_bank* bank, groove_envelope_params* out, uint32_t* enabled_out, uint32_t cap);
+int groove_bank_download_sample_envelope_state(groove_bank* bank, uint32_t* words);
 int groove_bank_destroy(groove_bank* bank);
 uint32_t groove_bank_voices(groove_bank* bank);
 /* HandlesMidi::handle_midi_message → PlaysNotes::note_on/note_off (orchestrator.rs:737-739;
@@ -291,7 +314,7 @@ int groove_bank_render_mix_deferred(groove_bank* bank, uint32_t frames, float* b
  * kind and at most 2,048 partial rows in all (config #5's share of one of eight GPUs: 8,192 Welsh + 4,096 FM + 4,096 sampler
  * voices, three launches whose durations added -> one); anything else is rendered bank by bank by groove_bank_render_mix_deferred in
  * the order given (bus = banks[0] (+)= ... ); a STEREO sampler bank among them, one whose sample
- * interpolation is not GROOVE_SAMPLE_NEAREST, or one with a looped sample always takes that bank-by-bank path (the one launch's
+ * interpolation is not GROOVE_SAMPLE_NEAREST, or one with a looped or enveloped sample always takes that bank-by-bank path (the one launch's
  * sampler body is the mono, nearest, loop-free one).  Bit-reproducible from run to run; the same sum as bank by bank to fp32 rounding, not
  * the same bits (one reduction over all rows instead of one per bank).  No reference counterpart as a call: the reference ticks
  * every instrument inside gather_audio. */
