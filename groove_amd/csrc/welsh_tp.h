@@ -22,7 +22,10 @@
 // A block of a voice is then ~1,500 instructions deep instead of ~25,000, at ~4x the total work: the right
 // trade exactly where the serial form leaves the machine idle.  groove_hip.hip picks this kernel for Welsh
 // banks of up to kTpMaxVoices voices and blocks of up to 256 frames; results agree with the serial kernels to
-// f64 rounding of the filter (1e-13 relative) and with the oracle to the same tolerance as they do.
+// f64 rounding of the filter and with the oracle to the same tolerance as they do.  (That rounding is not 1e-13 for every legal
+// coefficient set: measured per primitive on the MI355X, the scanned filter state stands up to 1.7e-11 of the state's largest
+// value off the serial fold — ripple 4.0 at 0.49 SR, and about as much at a 25 Hz cutoff — and bq_tp_wave's up to 1.5e-11;
+// docs/DSP_SPEC.md section 14.1, tests/test_gpu_wave_primitives.py.)
 //
 // The per-lane pieces are plain inline functions (host + device), so tests/emul runs the same text on the
 // CPU with a loop in place of the wavefront.

@@ -26,15 +26,19 @@ def _patches():
     return pats
 
 
-@pytest.mark.parametrize("vpw", [1, 2])
-def test_time_parallel_matches_serial_kernels_and_oracle(gpu_ctx, oracle, vpw):
-    """vpw = 2: the two-voices-per-wavefront form (welsh_tp_kernel<.., VPW = 2>: 32 lanes x 8 frames per voice) on a bank whose
+@pytest.mark.parametrize("vpw,extra", [pytest.param(1, 0, id="1"), pytest.param(1, 1, id="1-ragged"), pytest.param(2, 0, id="2")])
+def test_time_parallel_matches_serial_kernels_and_oracle(gpu_ctx, oracle, vpw, extra):
+    """vpw = 1 at two bank sizes: 3 voices on each of the 40 patches = 120, a multiple of the 4 voices per workgroup (every workgroup
+    full, the block leaves in 16-byte stores), and one voice more (n & 3 != 0: the scalar block stores, and one voice alone in the
+    last workgroup that has any).
+    vpw = 2: the two-voices-per-wavefront form (welsh_tp_kernel<.., VPW = 2>: 32 lanes x 8 frames per voice) on a bank whose
     adjacent voices share a patch — forced for this small bank by groove_set_time_parallel_pair_min_voices(1); the bank's size
     is odd, so the last wavefront holds one voice."""
     from groove_amd import entities as E
     pats = _patches()
     if vpw == 1:
-        n = len(pats) * 3        # three voices per patch, different keys; not a multiple of the 4 voices per workgroup
+        n = len(pats) * 3 + extra    # three voices per patch, different keys (and the first patch once more)
+        assert (n & 3 != 0) == bool(extra)
         params = (T.WelshParams * n)(*[pats[i % len(pats)] for i in range(n)])
     else:
         n = len(pats) * 2 + 1    # voices 2k and 2k + 1 on patch k; not a multiple of the 8 voices per workgroup
